@@ -12,6 +12,11 @@ inputs already resident in HBM (synthetic random-residue ciphertexts, BASELINE.m
 Rank 0 prints ONE JSON line.  Multi-GPU: blocks are sharded, one process per GPU, no data-path
 collective (weak scaling: 1024 blocks per GPU); RCCL is used for the barrier, the max-over-ranks
 time and an all-reduce of the output digests.
+
+A plain run sets up, warms up, times K steps and prints the headline line (with the rooflines of those steps).
+--full adds what needs work of its own: the bit-exact check against the CPU oracle and the output digest,
+the CPU baselines, and with N > 1 the in-run N = 1 leg and both gather legs.  --dump-outputs DIR
+writes a seeded sample of the last timed step's output ciphertexts (see dump_outputs).
 """
 import argparse
 import json
@@ -158,8 +163,8 @@ def issue_roofline(kernel_names, blocks, dev_ms_per_step):
 
 def ensure_world(gpus, script, argv):
     """`python bench.py --gpus N` is the WHOLE multi-GPU launch: without WORLD_SIZE in the environment and N > 1 the process
-    replaces itself by `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port
-    <free port> <script> <same arguments>` (one rank per GPU).  Under a launcher (WORLD_SIZE set) the two numbers must agree:
+    runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free port>
+    <script> <same arguments>` (one rank per GPU) as a child and exits with its status.  Under a launcher (WORLD_SIZE set) the two numbers must agree:
     a line measured on another number of ranks than --gpus says is refused, not printed.  More ranks than HIP devices is an
     error as well (RCCL refuses two ranks on one device) unless FHE_BENCH_BACKEND=gloo (tests: ranks share the devices)."""
     env_world = os.environ.get("WORLD_SIZE")
@@ -187,7 +192,9 @@ def ensure_world(gpus, script, argv):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")        # dmabuf IPC: RCCL between processes needs it on this driver
     sys.stdout.flush()
-    os.execvpe(sys.executable, cmd, env)
+    # a fresh child, not exec: this process may have opened the HIP runtime to count the devices
+    import subprocess
+    raise SystemExit(subprocess.call(cmd, env=env))
 
 
 _RCCL_PROBE_CHILD = r"""
@@ -318,6 +325,32 @@ def cpu_baseline_all_cores(blocks_per_thread=1):
             "sample": "%d blocks, OpenMP over blocks, %d threads, same oracle" % (nb, threads)}
 
 
+DUMP_SAMPLE_WORDS = 1 << 21                # 2 M words: 32 MiB of values + 16 MiB of positions, under the 64 MB cap
+DUMP_SEED = 20240607
+
+
+def dump_outputs(directory, out):
+    """--dump-outputs: the ciphertexts the last timed step wrote (this rank's shard, [blocks][64][2][k][n] u64 residues), as a fixed sample
+    that two builds can compare output for output.  The flat output is cut into DUMP_SAMPLE_WORDS equal strata and one seeded position is
+    drawn in each (every word when the output is smaller).  Residues reach 55 bits on some presets, more than float64 holds exactly, so
+      dct_quant_out_sample.npy        float64 [S, 2]: high and low 32 bits of each sampled word
+      dct_quant_out_sample_index.npy  float64 [S]: its position in the flat output"""
+    import numpy as np
+    import torch
+    words = out.numel()
+    if words <= DUMP_SAMPLE_WORDS:
+        pos = np.arange(words, dtype=np.int64)
+    else:
+        stride = words // DUMP_SAMPLE_WORDS
+        rng = np.random.default_rng(DUMP_SEED)
+        pos = np.arange(DUMP_SAMPLE_WORDS, dtype=np.int64) * stride + rng.integers(0, stride, DUMP_SAMPLE_WORDS, dtype=np.int64)
+    got = out.view(-1)[torch.from_numpy(pos).to(out.device)].cpu().numpy().view(np.uint64)
+    halves = np.stack([got >> np.uint64(32), got & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "dct_quant_out_sample.npy"), halves)
+    np.save(os.path.join(directory, "dct_quant_out_sample_index.npy"), pos.astype(np.float64))
+
+
 XGMI_LINK_GBS = 153.0                      # MI355X_MICROARCH.md: 7 xGMI links per GPU, ~153 GB/s each, point to point
 PCIE_GBS = 64.0                            # PCIe Gen5 x16 per direction (nominal); 55-60 GB/s is what pinned copies sustain
 
@@ -352,22 +385,31 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--blocks", type=int, default=1024, help="blocks per GPU per step")
-    ap.add_argument("--cpu-blocks", type=int, default=16, help="CPU baseline sample size (0 = skip)")
-    ap.add_argument("--no-verify", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: oracle check and output digest, CPU baselines, "
+                         "and with N > 1 the in-run N = 1 leg and the gather legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write a seeded sample of the last timed step's outputs as DIR/<name>.npy (float64; see dump_outputs)")
+    ap.add_argument("--cpu-blocks", type=int, default=16, help="CPU baseline sample size (0 = skip; --full only)")
+    ap.add_argument("--no-verify", action="store_true", help="skip the oracle check of --full")
     ap.add_argument("--preset", default="P4096", help="parameter set (default: the BASELINE.json configuration)")
     ap.add_argument("--gather", choices=["none", "wave", "local"], default="none",
                     help="what the TIMED region (`value`) does with the outputs.  wave: every wave of output ciphertexts is sent to rank 0 "
                          "(RCCL send/recv over xGMI, overlapped with the next wave's compute) and drained there by digest; local: every "
                          "rank drains ITS OWN waves to pinned host memory over its own PCIe link (parallel.LocalDrain; the consumer that "
                          "scales with the GPU count); none (default): outputs stay sharded in HBM (SURVEY.md 8e).  With N > 1 and the "
-                         "default, both gather variants are ALSO measured after the timed region and reported in `gather` (--gather-legs)")
+                         "default and --full, both gather variants are ALSO measured after the timed region and reported in `gather` (--gather-legs)")
     ap.add_argument("--gather-wave-blocks", type=int, default=64)
     ap.add_argument("--gather-legs", choices=["auto", "on", "off"], default="auto",
-                    help="the `gather` object of the line (with-gather figures next to the compute-only `value`): auto = when N > 1")
+                    help="the `gather` object of the line (with-gather figures next to the compute-only `value`): auto = when N > 1 with --full")
     ap.add_argument("--gather-steps", type=int, default=3, help="timed steps of each gather leg (one untimed step before them)")
     ap.add_argument("--n1-leg", choices=["auto", "on", "off"], default="auto",
-                    help="rank 0 alone times the same step before the all-rank region (in-run N = 1 figure -> weak_scaling.efficiency): auto = when N > 1")
+                    help="rank 0 alone times the same step before the all-rank region (in-run N = 1 figure -> weak_scaling.efficiency): auto = when N > 1 with --full")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs and args.gather != "none":
+        raise SystemExit("--dump-outputs needs --gather none: the gathered paths do not keep their outputs in HBM")
     ensure_world(args.gpus, os.path.abspath(__file__), sys.argv[1:])
 
     import numpy as np
@@ -407,7 +449,7 @@ def main():
     out = torch.empty_like(blocks)
     torch.cuda.synchronize()
 
-    legs = args.gather_legs == "on" or (args.gather_legs == "auto" and world > 1 and args.gather == "none")
+    legs = args.gather_legs == "on" or (args.gather_legs == "auto" and args.full and world > 1 and args.gather == "none")
     need_waves = args.gather != "none" or legs
     wave = n_waves = None
     if need_waves:
@@ -493,7 +535,7 @@ def main():
 
     # ---- in-run N = 1 leg: rank 0 alone, the other ranks idle at the barrier (weak scaling: the same B blocks per GPU) ----------------
     n1 = None
-    if args.n1_leg == "on" or (args.n1_leg == "auto" and world > 1):
+    if args.n1_leg == "on" or (args.n1_leg == "auto" and args.full and world > 1):
         barrier()
         if rank == 0:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -523,7 +565,10 @@ def main():
         rank_ms = [float(t[0].item()) for t in every]
         rank_dev_ms = [float(t[1].item()) for t in every]
 
-    # ---- verification: sampled blocks against the CPU oracle, digest over everything -----------------
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+
+    # ---- --full: verification (sampled blocks against the CPU oracle, digest over everything) -----------------
     def verify_local_drain():
         """the drained path ends in page-locked HOST buffers: one more pass whose consumer brings every drained wave back and digests
         it with its global index -- the bytes that really left over PCIe -- next to the digest of an in-HBM evaluation"""
@@ -542,21 +587,23 @@ def main():
         in_hbm = ctx.digest(out.view(-1), index0=first_index)
         return drained_digest, in_hbm
 
-    if args.gather == "local":
-        drained_digest, in_hbm = verify_local_drain()
-        if drained_digest != in_hbm:
-            raise SystemExit("--gather local: the waves drained to host memory differ from the in-HBM result (%016x != %016x)" % (drained_digest, in_hbm))
-        digest_all = fhe.parallel.combine_digests(in_hbm)
-    elif args.gather == "wave":     # the root holds the digest of every rank's last step; the ciphertexts were not kept
-        digest_all = int(wave_digests.cpu().numpy().view(np.uint64).sum(dtype=np.uint64)) if rank == 0 else 0
-        if gather is not None:
-            out = None
-        if dist is not None:
-            dist.barrier()
-    else:
-        digest_all = fhe.parallel.combine_digests(ctx.digest(out.view(-1), index0=first_index))
+    digest_all = None
+    if args.full:
+        if args.gather == "local":
+            drained_digest, in_hbm = verify_local_drain()
+            if drained_digest != in_hbm:
+                raise SystemExit("--gather local: the waves drained to host memory differ from the in-HBM result (%016x != %016x)" % (drained_digest, in_hbm))
+            digest_all = fhe.parallel.combine_digests(in_hbm)
+        elif args.gather == "wave":     # the root holds the digest of every rank's last step; the ciphertexts were not kept
+            digest_all = int(wave_digests.cpu().numpy().view(np.uint64).sum(dtype=np.uint64)) if rank == 0 else 0
+            if gather is not None:
+                out = None
+            if dist is not None:
+                dist.barrier()
+        else:
+            digest_all = fhe.parallel.combine_digests(ctx.digest(out.view(-1), index0=first_index))
     verified = None
-    if rank == 0 and not args.no_verify:
+    if rank == 0 and args.full and not args.no_verify:
         from oracle import oracle as om
         om.build()
         orc = om.Oracle.preset(args.preset)
@@ -614,7 +661,7 @@ def main():
                          "kernel": kernels + " (the launches of fhe_dct8x8_quant, all waves of one step; HIP events on the launch stream)",
                          "algorithmic_bytes_per_launch": B * bytes_per_block, "algorithmic_bytes_per_block": bytes_per_block,
                          "ms_per_launch": dev_ms_per_step},
-            "verified_bit_exact_vs_oracle": verified, "output_digest": "%016x" % digest_all,
+            "verified_bit_exact_vs_oracle": verified, "output_digest": None if digest_all is None else "%016x" % digest_all,
         }
         if world > 1:
             # per GPU above (rank 0's own events); the whole job beside it: every rank's algorithmic bytes over ITS device time, summed,
@@ -643,8 +690,8 @@ def main():
                     ir["frac"], ir["frac_at_nominal_clock"])
             res["roofline"]["limiter"] = ("valu-issue at the package power limit (see issue_roofline; 1.37 kW and sclk 2.13-2.20 GHz measured under this pair, "
                                           "profiles/r04_power_clocks_headline.txt, again in round 6: profiles/r06_power_clocks_headline.txt); the HBM fraction is reported because BASELINE.json's metric asks for it")
-        # SEAL's own CPU path "in the same run" (north_star): rank 0's host, every N; the other ranks wait at the barrier below
-        if args.cpu_blocks > 0 and args.preset == "P4096":
+        # SEAL's own CPU path "in the same run" (north_star, --full): rank 0's host, every N; the other ranks wait at the barrier below
+        if args.full and args.cpu_blocks > 0 and args.preset == "P4096":
             res["cpu_baseline"] = cpu_baseline(args.cpu_blocks)
             try:
                 res["cpu_baseline_all_cores"] = cpu_baseline_all_cores()

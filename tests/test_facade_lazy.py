@@ -149,4 +149,6 @@ def test_reference_server_jpeg_lazy_mode_on_the_48x48_image(fhe, tmp_path):
     line = [ln for ln in out.splitlines() if ln.startswith("RMSError,")]
     assert line and line[0].split(",")[1] == "1.71767", out[-500:]
     print("server_jpeg 48x48: eager %.2f s, lazy %.2f s; %s" % (wall["eager"], wall["lazy"], stats))
-    assert wall["lazy"] < wall["eager"]
+    # ctx_create_ms holds the device runtime's start-up, which does not depend on the mode and varies by a second on a shared machine
+    work = {m: wall[m] - stats[m]["ctx_create_ms"] * 1e-3 for m in wall}
+    assert work["lazy"] < work["eager"], work

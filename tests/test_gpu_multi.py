@@ -17,14 +17,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _bench(args, nproc=1, **extra_env):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
     if nproc == 1:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + args
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + args
     else:
         s = socket.socket()
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
         s.close()
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
-               "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc)] + args
+               "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--full"] + args
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -76,10 +76,10 @@ def _direct(script, args, **extra_env):
 
 
 def test_bench_gpus_2_is_the_whole_launch():
-    """`python bench.py --gpus 2` by itself starts two ranks (bench.ensure_world re-executes under torch.distributed.run); on a
+    """`python bench.py --gpus 2` by itself starts two ranks (bench.ensure_world runs torch.distributed.run as a child); on a
     one-GPU box the ranks share the device over gloo.  n_gpus == rccl_ranks == 2 and 2 x 128 blocks == 1 x 256 blocks by digest."""
     one = _bench(["--blocks", "256", "--steps", "1", "--warmup", "0", "--cpu-blocks", "0"])
-    r = _direct("bench.py", ["--gpus", "2", "--blocks", "128", "--steps", "2", "--warmup", "1", "--cpu-blocks", "0"], FHE_BENCH_BACKEND="gloo")
+    r = _direct("bench.py", ["--gpus", "2", "--full", "--blocks", "128", "--steps", "2", "--warmup", "1", "--cpu-blocks", "0"], FHE_BENCH_BACKEND="gloo")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     two = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert two["n_gpus"] == 2 and two["rccl_ranks"] == 2 and len(two["ms_per_step_per_rank"]) == 2
@@ -87,13 +87,13 @@ def test_bench_gpus_2_is_the_whole_launch():
 
 
 def test_the_one_driver_command_prints_the_whole_multi_gpu_record():
-    """`python bench.py --gpus 2 --steps 3` -- the command the driver runs at N > 1, nothing else on the line -- prints ONE JSON line that
+    """`python bench.py --gpus 2 --full --steps 3` -- the driver's command at N > 1 with --full -- prints ONE JSON line that
     carries the compute-only `value`, the CPU baseline of the same run, an in-run N = 1 leg with the weak-scaling efficiency, BOTH
     gather legs (wave-to-root with its xGMI link ceiling, local PCIe drain) and the aggregate roofline.  On a one-GPU box the two ranks
     share the device over gloo (FHE_BENCH_BACKEND=gloo): the schema and every code path of the record, not the physics."""
     import torch
     shared = torch.cuda.device_count() < 2
-    r = _direct("bench.py", ["--gpus", "2", "--steps", "3", "--warmup", "1", "--blocks", "256", "--cpu-blocks", "2"], **({"FHE_BENCH_BACKEND": "gloo"} if shared else {}))
+    r = _direct("bench.py", ["--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--blocks", "256", "--cpu-blocks", "2"], **({"FHE_BENCH_BACKEND": "gloo"} if shared else {}))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -123,7 +123,7 @@ def test_a_gather_leg_that_hangs_is_abandoned_and_the_line_still_appears():
     """the RCCL wave gather has never run between two devices: a leg that does not complete must not take the line with it.  With
     FHE_BENCH_GATHER_TIMEOUT=0.001 the watchdog of the first leg fires at once on every rank: rank 0 prints the line measured so far
     (value, cpu_baseline, weak_scaling) with the leg marked, and every rank leaves with exit code 0."""
-    r = _direct("bench.py", ["--gpus", "2", "--steps", "2", "--warmup", "1", "--blocks", "128", "--cpu-blocks", "0"], FHE_BENCH_BACKEND="gloo", FHE_BENCH_GATHER_TIMEOUT="0.001")
+    r = _direct("bench.py", ["--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--blocks", "128", "--cpu-blocks", "0"], FHE_BENCH_BACKEND="gloo", FHE_BENCH_GATHER_TIMEOUT="0.001")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["weak_scaling"]["efficiency"] > 0
@@ -156,7 +156,7 @@ def test_one_rank_process_group_runs_the_collectives_on_rccl():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", FHE_BENCH_FORCE_DIST="1")
     env.pop("FHE_BENCH_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--blocks", "128", "--steps", "2", "--warmup", "1", "--cpu-blocks", "0"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--blocks", "128", "--steps", "2", "--warmup", "1", "--cpu-blocks", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     one = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -180,7 +180,7 @@ def test_rccl_probe_and_its_gloo_fall_back_under_the_launcher(fail):
     if fail:
         env["FHE_BENCH_PROBE_FAIL"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--blocks", "128", "--steps", "2", "--warmup", "1", "--cpu-blocks", "0"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--blocks", "128", "--steps", "2", "--warmup", "1", "--cpu-blocks", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     one = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -14,11 +14,11 @@ cp $O/pmc_traffic_ctct.json profiles/pmc_traffic_ctct.json
 python tools/collect_traffic.py circuits > $O/collect_traffic_circuits.log 2>&1; cp gpurun_out/pmc_traffic_circuits.json $O/pmc_traffic_circuits.json
 python tools/collect_traffic.py encrypt > $O/collect_traffic_encrypt.log 2>&1; cp gpurun_out/pmc_traffic_encrypt.json $O/pmc_traffic_encrypt.json
 cp $O/pmc_traffic.json profiles/pmc_traffic.json
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --cpu-blocks 0 > $O/bench_default_with_traffic.json 2>/dev/null
-python bench.py --cpu-blocks 0 --blocks 8192 --steps 3 --warmup 1 > $O/bench_config4_share_8192.json 2>/dev/null
-python bench.py --cpu-blocks 0 --gather local --steps 3 --warmup 1 > $O/bench_gather_local.json 2>/dev/null
-for p in SEAL23_4096 SEAL3_8192 P8192; do python bench.py --preset $p --cpu-blocks 0 --steps 5 --blocks 512 > $O/bench_$p.json 2>/dev/null; done
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --cpu-blocks 0 > $O/bench_default_with_traffic.json 2>/dev/null
+python bench.py --full --cpu-blocks 0 --blocks 8192 --steps 3 --warmup 1 > $O/bench_config4_share_8192.json 2>/dev/null
+python bench.py --full --cpu-blocks 0 --gather local --steps 3 --warmup 1 > $O/bench_gather_local.json 2>/dev/null
+for p in SEAL23_4096 SEAL3_8192 P8192; do python bench.py --full --preset $p --cpu-blocks 0 --steps 5 --blocks 512 > $O/bench_$p.json 2>/dev/null; done
 python tools/bench_ops.py P4096 4096 > $O/bench_ops_P4096.txt 2>&1
 python tools/bench_ops.py P8192 2048 > $O/bench_ops_P8192.txt 2>&1
 FHE_BEHZ_FUSED_PREPARE=1 python tools/bench_ops.py P8192 2048 > $O/bench_ops_P8192_fused_prepare.txt 2>&1
@@ -53,7 +53,7 @@ for m in device host; do python tools/bench_server_decode.py --encrypt $m 2>/dev
 fully-homomorphic-image-processing_amd/seal/multi_gpu_dct 1024 4 64 1 > $O/cpp_multi_gpu_dct.json 2>&1
 fully-homomorphic-image-processing_amd/seal/multi_gpu_dct 1024 1 256 0 resident 20 > $O/cpp_multi_gpu_dct_resident.json 2>&1
 # the one command the driver runs at N > 1, on this one device over gloo (schema + every leg; the physics needs N devices)
-FHE_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 5 --warmup 2 > $O/bench_world2_gloo_one_device.json 2>/dev/null
+FHE_BENCH_BACKEND=gloo python bench.py --gpus 2 --full --steps 5 --warmup 2 > $O/bench_world2_gloo_one_device.json 2>/dev/null
 FHE_BENCH_BACKEND=gloo python bench_circuits.py resize --shared --gpus 2 > $O/bench_circuits_resize_shared_world2_gloo.json 2>/dev/null
 python tools/results_table.py > $O/results_table.json 2>/dev/null
 FHE_ENC_UNFUSED=1 python tools/bench_encrypt.py P8192 512 2>/dev/null | tail -1 | sed 's/^/UNFUSED /' >> $O/bench_encrypt.txt

@@ -10,4 +10,4 @@ for ln in sys.stdin:
     except Exception: continue
     print('$tag', d.get('op'), {k: (round(v, 1) if isinstance(v, float) else v) for k, v in d.items() if k != 'op'})
 "
-for p in SEAL23_4096 P8192; do python bench.py --preset $p --cpu-blocks 0 --steps 5 --blocks 512 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$tag', '$p', round(d['value']), d['verified_bit_exact_vs_oracle'])"; done
+for p in SEAL23_4096 P8192; do python bench.py --full --preset $p --cpu-blocks 0 --steps 5 --blocks 512 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$tag', '$p', round(d['value']), d['verified_bit_exact_vs_oracle'])"; done
