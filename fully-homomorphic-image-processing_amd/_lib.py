@@ -90,6 +90,11 @@ SIGNATURES = {
     "fhe_dct8x8_quant": (_i, [_vp, _vp, _vp, _vp, _u64, _vp, _sz, _vp]),
     "fhe_rgb_to_ycc": (_i, [_vp, _vp, _vp, _vp, _u64, _i, _i, _vp]),
     "fhe_rgb_to_ycc_blocks": (_i, [_vp, _vp, _u64, _i, _i, _vp]),
+    "fhe_idct_plan_create": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(_vp)]),
+    "fhe_idct_plan_destroy": (_i, [_vp]),
+    "fhe_idct8x8_scratch_bytes": (_sz, [_vp, _u64]),
+    "fhe_idct8x8_dequant": (_i, [_vp, _vp, _vp, _vp, _u64, _vp, _sz, _vp]),
+    "fhe_ycc_to_rgb_blocks": (_i, [_vp, _vp, _u64, _i, _i, _vp]),
     "fhe_fill_random": (_i, [_vp, _vp, _u64, _u64, _u64, _vp]),
     "fhe_digest": (_i, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "fhe_count_unreduced": (_i, [_vp, _vp, _u64, _vp, _vp]),

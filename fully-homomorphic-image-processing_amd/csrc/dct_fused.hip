@@ -850,3 +850,198 @@ int fhe_poly_f64_launch(int mode, const fhe_ctx *c, const u64 *in, u64 *out, u64
     KERNEL_CHECK();
     return FHE_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// The inverse: dequantisation + 8x8 IDCT (fhe_idct8x8_dequant, idct.hip) as the same two fused launches
+// ------------------------------------------------------------------------------------------------
+// The butterfly of an inverse line sits on the OUTPUT side (out[m] = E[m] + O[m], out[7-m] = E[m] - O[m]; E from the even
+// inputs d0 d2 d4 d6, O from the odd ones d1 d3 d5 d7), so the halves split on the inputs:
+//   k_idct_rows: the even workgroup of a row takes inputs 0, 2, 4, 6, the odd one 1, 3, 5, 7 (8 apart in blockIdx, one
+//                XCD); four joint forward NTTs, per slot the input product (encode(Q[i]) * encode(0.125), folded by the
+//                plan) and the half line; E[0..3] / O[0..3] stored in NTT form at ciphertexts 8 row + 0..3 / 8 row + 4..7
+//   k_idct_cols: each of the two workgroups of a column forms the column's eight inputs as E +- O while it loads (exact
+//                adds in the NTT domain), evaluates the whole line per slot, keeps outputs 0..3 or 4..7 and runs four
+//                joint inverse NTTs.
+// Bounds (units of p; every product mm(y, w) below has |y| <= 4 p and a centred |w| <= p/2, so |r| <= p/2 + 6 p^2 2^-53 < 0.6 p
+// for p < 2^47; red(x) returns |x - round(x / p) p| <= p/2 up to the same kind of term):
+//   rows:  after the forward NTT each value is reduced (red: |x| <= p/2); input products < 0.6 p; even part t0, t1 < 1.2 p,
+//          t2, t3 < 1.2 p, E < 2.4 p; odd part: up to three products summed after the fourth, O < 2.4 p; both reduced again
+//          before the store (|.| <= p/2)
+//   cols:  inputs E +- O < p; even part: d2 + d6 < 2 p, t0 < 2 p, t3 < 1.2 p, E' < 3.2 p; odd part: z3 + z4 < 4 p (the
+//          largest product operand), O' < 2.4 p; outputs < 5.6 p, reduced before the inverse NTT (|.| <= p/2), whose
+//          passes reduce between them for primes above 40 bits as the forward columns do.
+// Everything stays far below 2^53: the arithmetic is exact and the residues equal the op-by-op evaluation.
+namespace {
+using namespace fp64;
+
+// Half of an inverse line on one NTT slot.  HALF 0: v = d0 d2 d4 d6 -> E0..E3 (t10 t11 t12 t13);  HALF 1: v = d1 d3 d5 d7 ->
+// O0..O3 (u3 u2 u1 u0 of the specification).  c[] = the twelve line constants at this slot.
+template <int HALF>
+__device__ __forceinline__ void idct_half(double (&v)[4], const double (&c)[12], double p, double pinv) {
+    if constexpr (HALF == 0) {
+        double y[3] = {v[1] + v[3], v[3], v[1]};
+        const double w[3] = {c[0], c[2], c[1]};
+        mmv<3>(y, w, p, pinv);
+        const double t2 = y[0] + y[1], t3 = y[0] + y[2], t0 = v[0] + v[2], t1 = v[0] - v[2];
+        v[0] = t0 + t3;
+        v[1] = t1 + t2;
+        v[2] = t1 - t2;
+        v[3] = t0 - t3;
+    } else {
+        const double u0 = v[3], u1 = v[2], u2 = v[1], u3 = v[0];
+        const double z1 = u0 + u3, z2 = u1 + u2, z3 = u0 + u2, z4 = u1 + u3;
+        double ya[5] = {z3 + z4, u0, u1, u2, u3}, yb[4] = {z1, z2, z3, z4};
+        const double wa[5] = {c[3], c[4], c[5], c[6], c[7]}, wb[4] = {c[8], c[9], c[10], c[11]};
+        mmv<5>(ya, wa, p, pinv);
+        mmv<4>(yb, wb, p, pinv);
+        const double z3b = yb[2] + ya[0], z4b = yb[3] + ya[0];
+        v[0] = ya[4] + yb[0] + z4b;        // O0 = u3' + z1' + z4'
+        v[1] = ya[3] + yb[1] + z3b;        // O1 = u2' + z2' + z3'
+        v[2] = ya[2] + yb[1] + z4b;        // O2 = u1' + z2' + z4'
+        v[3] = ya[1] + yb[0] + z3b;        // O3 = u0' + z1' + z3'
+    }
+}
+
+template <int L, int LE, int HALF>
+__device__ __forceinline__ void irows_body(const u64 *__restrict__ in, double *__restrict__ mid, const double *__restrict__ consts,
+                                           const double *__restrict__ tw, const Work &wk, double p, double pinv, u32 k, double *lds) {
+    using SH = Shape<L, LE>;
+    constexpr int N = SH::N, TP = SH::TP, E = SH::E;
+    const int tid = threadIdx.x;
+    const size_t poly_words = (size_t)k * N, ct_words = 2 * poly_words, cstride = (size_t)k * N;
+    const size_t base = ((size_t)wk.blk * 64 + 8 * wk.line) * ct_words + (size_t)wk.poly * poly_words + (size_t)wk.prime * N + tid;
+    double w0[E - 1];
+    load_tw<L, LE, 0>(w0, tw, tid);
+    double x[4][E];
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+        const u64 *a = in + base + (size_t)(2 * m + HALF) * ct_words;
+#pragma unroll
+        for (int r = 0; r < E; r++) x[m][r] = u52_to_f64(a[r * TP]);
+        asm volatile("" ::: "memory");
+    }
+    int phase = 0;
+    ntt_fwd<L, LE, 4>(x, w0, tw, p, pinv, lds, tid, phase, [] {});
+    const double *cp = consts + (size_t)wk.prime * N + tid;
+#pragma unroll
+    for (int r = 0; r < E; r++) {
+        double c[12], s[4], v[4];
+#pragma unroll
+        for (int i = 0; i < 12; i++) c[i] = cp[(size_t)i * cstride + r * TP];
+#pragma unroll
+        for (int m = 0; m < 4; m++) {
+            s[m] = cp[(size_t)(12 + 8 * wk.line + 2 * m + HALF) * cstride + r * TP];
+            v[m] = red(x[m][r], p, pinv);
+        }
+        mmv<4>(v, s, p, pinv);
+        idct_half<HALF>(v, c, p, pinv);
+#pragma unroll
+        for (int m = 0; m < 4; m++) x[m][r] = red(v[m], p, pinv);
+    }
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+        double *o = mid + base + (size_t)(4 * HALF + m) * ct_words;
+#pragma unroll
+        for (int r = 0; r < E; r++) o[r * TP] = x[m][r];
+    }
+}
+
+template <int L, int LE>
+__global__ __launch_bounds__((Shape<L, LE>::TP), (Occ<L, LE>::W)) void k_idct_rows(const u64 *__restrict__ in, double *__restrict__ mid,
+                                                                   const double *__restrict__ consts, const double *__restrict__ tw_all,
+                                                                   const Modulus *__restrict__ mods, u32 k) {
+    __shared__ double lds[2 * Shape<L, LE>::LDS_WORDS];
+    const Work wk = decode(blockIdx.x, k);   // line = row index
+    const double p = (double)mods[wk.prime].q, pinv = 1.0 / p;
+    const double *tw = tw_all + (size_t)wk.prime * Shape<L, LE>::N;
+    if (wk.half) irows_body<L, LE, 1>(in, mid, consts, tw, wk, p, pinv, k, lds);
+    else irows_body<L, LE, 0>(in, mid, consts, tw, wk, p, pinv, k, lds);
+}
+
+template <int L, int LE, bool BIG, int HALF>
+__device__ __forceinline__ void icols_body(const double *__restrict__ mid, u64 *__restrict__ out, const double *__restrict__ consts,
+                                           const double *__restrict__ itw, const Work &wk, double p, double pinv, u32 k, double *lds) {
+    using SH = Shape<L, LE>;
+    constexpr int N = SH::N, TP = SH::TP, E = SH::E, LASTP = SH::NP - 1;
+    const int tid = threadIdx.x;
+    const size_t poly_words = (size_t)k * N, ct_words = 2 * poly_words, cstride = (size_t)k * N;
+    const size_t base = (size_t)wk.blk * 64 * ct_words + (size_t)wk.poly * poly_words + (size_t)wk.prime * N + tid;
+    const u32 col = wk.line, m = col < 4 ? col : 7 - col;      // row output `col` = E[m] + O[m] (col < 4) or E[m] - O[m]
+    const bool neg = col >= 4;
+    const double *cp = consts + (size_t)wk.prime * N + tid;
+    double x[4][E];
+#pragma unroll
+    for (int r = 0; r < E; r++) {
+        double d[8], c[12];
+#pragma unroll
+        for (int rr = 0; rr < 8; rr++) {
+            const double A = mid[base + (size_t)(8 * rr + m) * ct_words + r * TP], B = mid[base + (size_t)(8 * rr + 4 + m) * ct_words + r * TP];
+            d[rr] = neg ? A - B : A + B;
+        }
+#pragma unroll
+        for (int i = 0; i < 12; i++) c[i] = cp[(size_t)i * cstride + r * TP];
+        double ev[4] = {d[0], d[2], d[4], d[6]}, od[4] = {d[1], d[3], d[5], d[7]};
+        idct_half<0>(ev, c, p, pinv);
+        idct_half<1>(od, c, p, pinv);
+#pragma unroll
+        for (int j = 0; j < 4; j++) x[j][r] = red(HALF ? ev[3 - j] - od[3 - j] : ev[j] + od[j], p, pinv);
+    }
+    double wl[E - 1];
+    load_tw<L, LE, LASTP>(wl, itw, tid);
+    int phase = 0;
+    ntt_inv<L, LE, 4, BIG>(x, wl, itw, p, pinv, lds, tid, phase);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        u64 *o = out + base + (size_t)(8 * (4 * HALF + j) + col) * ct_words;
+#pragma unroll
+        for (int r = 0; r < E; r++) {
+            double v = x[j][r];
+            v = v < 0.0 ? v + p : v;
+            o[r * TP] = f64_to_u52(v);
+        }
+    }
+}
+
+template <int L, int LE, bool BIG>
+__global__ __launch_bounds__((Shape<L, LE>::TP), (Occ<L, LE>::W)) void k_idct_cols(const double *__restrict__ mid, u64 *__restrict__ out,
+                                                                   const double *__restrict__ consts, const double *__restrict__ itw_all,
+                                                                   const Modulus *__restrict__ mods, u32 k) {
+    __shared__ double lds[2 * Shape<L, LE>::LDS_WORDS];
+    const Work wk = decode(blockIdx.x, k);   // line = column index
+    const double p = (double)mods[wk.prime].q, pinv = 1.0 / p;
+    const double *itw = itw_all + (size_t)wk.prime * Shape<L, LE>::N;
+    if (wk.half) icols_body<L, LE, BIG, 1>(mid, out, consts, itw, wk, p, pinv, k, lds);
+    else icols_body<L, LE, BIG, 0>(mid, out, consts, itw, wk, p, pinv, k, lds);
+}
+
+template <int L, int LE>
+void launch_ipair(const fhe_ctx *c, const double *consts, const u64 *in, u64 *out, double *mid, unsigned grid, bool big, hipStream_t st) {
+    constexpr int TP = Shape<L, LE>::TP;
+    k_idct_rows<L, LE><<<grid, TP, 0, st>>>(in, mid, consts, c->qb.d_tw_f64, c->qb.d_mod, c->k);
+    if (big) k_idct_cols<L, LE, true><<<grid, TP, 0, st>>>(mid, out, consts, c->qb.d_itw_f64, c->qb.d_mod, c->k);
+    else k_idct_cols<L, LE, false><<<grid, TP, 0, st>>>(mid, out, consts, c->qb.d_itw_f64, c->qb.d_mod, c->k);
+}
+}  // namespace
+
+int fhe_idct_f64_make_consts(const fhe_ctx *c, const ulonglong2 *d_consts, double **out, hipStream_t st) {
+    const u32 total = DCT_NCONST * c->k * c->n;
+    HIP_TRY(hipMalloc(out, sizeof(double) * total));
+    k_consts_to_f64<<<(total + 255) / 256, 256, 0, st>>>(d_consts, *out, c->qb.d_mod, c->k, c->n, dct_shape_le(c), total);
+    KERNEL_CHECK();
+    return FHE_OK;
+}
+
+int fhe_idct_f64_launch(const fhe_ctx *c, const double *consts, const u64 *in, u64 *out, u64 n_blocks, double *mid, hipStream_t st) {
+    const u64 grid = n_blocks * 8 * 2 * c->k * 2;   // (block, line, poly, prime) x two halves
+    if (grid > 0x7fffffffULL) return fail(FHE_ERR_PARAM, "too many blocks for one launch");
+    const bool big = c->max_prime_bits > 40;
+    switch (c->logn) {   // the forward pair's shapes (dct_shape_le)
+        case 10: launch_ipair<10, 4>(c, consts, in, out, mid, (unsigned)grid, big, st); break;
+        case 11: launch_ipair<11, 3>(c, consts, in, out, mid, (unsigned)grid, big, st); break;
+        case 12: if (dct_shape_le(c) == 3) launch_ipair<12, 3>(c, consts, in, out, mid, (unsigned)grid, big, st); else launch_ipair<12, 4>(c, consts, in, out, mid, (unsigned)grid, big, st); break;
+        case 13: if (dct_shape_le(c) == 3) launch_ipair<13, 3>(c, consts, in, out, mid, (unsigned)grid, big, st); else launch_ipair<13, 4>(c, consts, in, out, mid, (unsigned)grid, big, st); break;
+        default: return fail(FHE_ERR_PARAM, "fused FP64 path supports n in {1024, 2048, 4096, 8192}");
+    }
+    KERNEL_CHECK();
+    return FHE_OK;
+}

@@ -311,6 +311,11 @@ extern "C" int fhe_ctx_destroy(fhe_ctx *c) {
         if (r->d_off) (void)hipFree(r->d_off);
         delete r;
     }
+    for (fhe_ctx::RgbConsts *r : c->ycc) {
+        if (r->d_c) (void)hipFree(r->d_c);
+        if (r->d_off) (void)hipFree(r->d_off);
+        delete r;
+    }
     fhe_behz_free(c);
     fhe_free_base(c->qb);
     delete c;
@@ -1304,7 +1309,7 @@ extern "C" int fhe_dyadic_multiply(const fhe_ctx *c, const uint64_t *a, const ui
 // Constant table: [cid][prime][n] Shoup pairs in slot order.
 //   cid 0..11  : the twelve LL&M constants of homo/fhe_image.h:221-236, in order of first use
 //   cid 12..75 : per-output scale = encode(0.125) [* encode(1/quant[i])], i = row-major output index
-static const double kDctConst[12] = {0.541196100, 0.765366865, -1.847759065, 1.175875602, 0.298631336, 2.053119869,
+const double kDctConst[12] = {0.541196100, 0.765366865, -1.847759065, 1.175875602, 0.298631336, 2.053119869,
                                      3.072711026, 1.501321110, -0.899976223, -2.562915447, -1.961570560, -0.390180644};
 // One 1-D LL&M pass on eight fully reduced residues (same dataflow as homo/fhe_image.h:207-242).
 // C(cid) yields the Shoup pair of constant cid at this thread's slot.

@@ -109,10 +109,12 @@ struct fhe_ctx {
         u32 off_len = 0;
     };
     mutable std::vector<RgbConsts *> rgb;
+    mutable std::vector<RgbConsts *> ycc;     // the same for ycc_to_rgb (idct.hip): four factors, d_c_f64 unused; under rgb_mutex
     mutable std::mutex rgb_mutex;
 };
 
 #define DCT_NCONST 76
+extern const double kDctConst[12];   // the twelve LL&M constants shared by the forward (fhe_hip.hip) and inverse (idct.hip) lines
 struct fhe_dct_plan {
     ulonglong2 *d_consts = nullptr;   // [DCT_NCONST][k][n] Shoup pairs, slot order
     double *d_consts_f64 = nullptr;   // [DCT_NCONST][k][n] centred doubles (FP64 path), or null
@@ -183,6 +185,9 @@ int fhe_dct_f64_make_consts(const fhe_ctx *c, fhe_dct_plan *plan, hipStream_t st
 bool fhe_dct_u64_supported(const fhe_ctx *c);
 int fhe_dct_u64_make_consts(const fhe_ctx *c, fhe_dct_plan *plan, hipStream_t st);
 int fhe_dct_u64_launch(const fhe_ctx *c, const fhe_dct_plan *plan, const u64 *in, u64 *out, u64 n_blocks, u64 *mid, hipStream_t st);
+// fused FP64 inverse pair k_idct_rows + k_idct_cols (dct_fused.hip); consts: the idct plan's table in the fused kernels' order
+int fhe_idct_f64_make_consts(const fhe_ctx *c, const ulonglong2 *d_consts, double **out, hipStream_t st);
+int fhe_idct_f64_launch(const fhe_ctx *c, const double *consts, const u64 *in, u64 *out, u64 n_blocks, double *mid, hipStream_t st);
 bool fhe_rgb_f64_supported(const fhe_ctx *c);
 int fhe_poly_f64_launch(int mode, const fhe_ctx *c, const u64 *in, u64 *out, u64 n_polys, const ulonglong2 *plain, hipStream_t st);
 int fhe_rgb_f64_make_consts(const fhe_ctx *c, const ulonglong2 *d_c, double **out, hipStream_t st);

@@ -224,6 +224,30 @@ class DctPlan:
             self.h = None
 
 
+class IdctPlan:
+    """Constants of fhe_idct8x8_dequant: dequantisation by `quant` (None: skipped), the twelve line constants, the 1/8 scale."""
+
+    def __init__(self, ctx, quant=YQT, int_coeffs=100, frac_coeffs=100):
+        self.ctx = ctx
+        h = C.c_void_p()
+        qv = None
+        if quant is not None:
+            if len(quant) != 64:
+                raise ValueError("IdctPlan: a quantisation table has 64 entries, got %d" % len(quant))
+            qv = (C.c_double * 64)(*[float(x) for x in quant])
+        _lib.call("fhe_idct_plan_create", ctx.h, qv, int_coeffs, frac_coeffs, _stream(), C.byref(h))
+        self.h = h
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h:
+            try:
+                _lib.load().fhe_idct_plan_destroy(h)
+            except Exception:
+                pass
+            self.h = None
+
+
 def check_evaluation_keys(ctx, evk_ntt, dbc, need, who):
     """The library takes the keys as a bare pointer and reads need * fhe_evk_words(ctx, dbc) words behind it (include/fhe_hip.h): the host
     checks that the tensor it hands over holds them -- a key tensor made for another decomposition bit count (fewer digits), another context or
@@ -473,4 +497,34 @@ class Evaluator:
         assert blocks.shape[-5:] == (3, 64, 2, self.ctx.k, self.ctx.n) and blocks.is_contiguous()
         n_blocks = blocks.numel() // (3 * 64 * 2 * self.ctx.k * self.ctx.n)
         _lib.call("fhe_rgb_to_ycc_blocks", self.ctx.h, _ptr(blocks), n_blocks, int_coeffs, frac_coeffs, _stream())
+        return blocks
+
+    def idct8x8_dequant(self, plan, blocks, out=None):
+        """dequantisation + 8x8 inverse DCT on [n_blocks, 64, 2, k, n], the inverse of dct8x8_quant (include/fhe_hip.h)."""
+        shape = (64, 2, self.ctx.k, self.ctx.n)
+        if not (isinstance(blocks, torch.Tensor) and blocks.dim() >= 4 and tuple(blocks.shape[-4:]) == shape and blocks.dtype == torch.int64
+                and blocks.is_contiguous() and blocks.device == self.ctx.device):
+            raise ValueError("idct8x8_dequant: `blocks` must be a contiguous int64 tensor [..., 64, 2, k, n] = [..., %d, %d, %d, %d] on the "
+                             "context's device, got %r" % (shape + (tuple(getattr(blocks, "shape", ())),)))
+        if plan.ctx.k != self.ctx.k or plan.ctx.n != self.ctx.n:
+            raise ValueError("idct8x8_dequant: the plan was built for another context")
+        if out is not None and (out.shape != blocks.shape or out.dtype != blocks.dtype or not out.is_contiguous() or out.device != blocks.device):
+            raise ValueError("idct8x8_dequant: `out` must be a contiguous tensor like `blocks` (%r), got %r" % (tuple(blocks.shape), tuple(out.shape)))
+        out = torch.empty_like(blocks) if out is None else out
+        n_blocks = blocks.numel() // (64 * 2 * self.ctx.k * self.ctx.n)
+        nbytes = _lib.load().fhe_idct8x8_scratch_bytes(self.ctx.h, n_blocks)
+        scr = self._scratch_buf(nbytes)
+        _lib.call("fhe_idct8x8_dequant", self.ctx.h, plan.h, _ptr(blocks), _ptr(out), n_blocks, _ptr(scr), nbytes, _stream())
+        return out
+
+    def ycc_to_rgb_blocks(self, blocks, int_coeffs=100, frac_coeffs=100):
+        """JFIF YCbCr -> RGB on the stream layout [n_blocks, 3, 64, 2, k, n] (64 Y, 64 Cb, 64 Cr per block), in place: the inverse of
+        rgb_to_ycc_blocks."""
+        shape = (3, 64, 2, self.ctx.k, self.ctx.n)
+        if not (isinstance(blocks, torch.Tensor) and blocks.dim() >= 5 and tuple(blocks.shape[-5:]) == shape and blocks.dtype == torch.int64
+                and blocks.is_contiguous() and blocks.device == self.ctx.device):
+            raise ValueError("ycc_to_rgb_blocks: `blocks` must be a contiguous int64 tensor [..., 3, 64, 2, k, n] = [..., %d, %d, %d, %d, %d] on "
+                             "the context's device, got %r" % (shape + (tuple(getattr(blocks, "shape", ())),)))
+        n_blocks = blocks.numel() // (3 * 64 * 2 * self.ctx.k * self.ctx.n)
+        _lib.call("fhe_ycc_to_rgb_blocks", self.ctx.h, _ptr(blocks), n_blocks, int_coeffs, frac_coeffs, _stream())
         return blocks

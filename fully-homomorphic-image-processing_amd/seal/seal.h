@@ -1586,6 +1586,42 @@ inline void dct8x8_quant(const SEALContext &ctx, std::vector<Ciphertext> &data, 
     for (size_t i = 0; i < data.size(); ++i) detail::check(fhe_copy(data[i].ptr(), out.ptr() + i * ctw, ctw * 8, nullptr), "copy");
     detail::check(fhe_stream_sync(nullptr), "sync");
 }
+// the way back: dequantisation by `quant` (null: skipped) + 8x8 inverse DCT on whole blocks (64 ciphertexts each), in one call
+inline void idct8x8_dequant(const SEALContext &ctx, std::vector<Ciphertext> &data, const std::vector<double> *quant,
+                            int int_coeffs = 100, int frac_coeffs = 100) {
+    const detail::CtxState &s = *ctx.state();
+    if (data.empty() || data.size() % 64) throw std::invalid_argument("idct8x8_dequant needs a multiple of 64 ciphertexts");
+    if (quant && quant->size() != 64) throw std::invalid_argument("idct8x8_dequant needs a 64-entry quantisation table");
+    const size_t ctw = 2 * s.poly_words(), blocks = data.size() / 64;
+    detail::DevBuf buf(data.size() * ctw);
+    for (size_t i = 0; i < data.size(); ++i) {
+        if (data[i].size() != 2) throw std::invalid_argument("idct8x8_dequant needs size-2 ciphertexts");
+        detail::check(fhe_copy(buf.ptr() + i * ctw, data[i].ptr(), ctw * 8, nullptr), "copy");
+    }
+    fhe_idct_plan *plan = nullptr;
+    detail::check(fhe_idct_plan_create(s.h, quant ? quant->data() : nullptr, int_coeffs, frac_coeffs, nullptr, &plan), "idct plan");
+    const size_t bytes = fhe_idct8x8_scratch_bytes(s.h, blocks);
+    detail::DevBuf scratch((bytes + 7) / 8 + 1);
+    int rc = fhe_idct8x8_dequant(s.h, plan, buf.ptr(), buf.ptr(), blocks, scratch.ptr(), bytes, nullptr);
+    fhe_idct_plan_destroy(plan);
+    detail::check(rc, "idct8x8_dequant");
+    for (size_t i = 0; i < data.size(); ++i) detail::check(fhe_copy(data[i].ptr(), buf.ptr() + i * ctw, ctw * 8, nullptr), "copy");
+    detail::check(fhe_stream_sync(nullptr), "sync");
+}
+// JFIF YCbCr -> RGB on the stream order (per block 64 Y, 64 Cb, 64 Cr ciphertexts), in place -> 64 R, 64 G, 64 B
+inline void ycc_to_rgb_blocks(const SEALContext &ctx, std::vector<Ciphertext> &data, int int_coeffs = 100, int frac_coeffs = 100) {
+    const detail::CtxState &s = *ctx.state();
+    if (data.empty() || data.size() % 192) throw std::invalid_argument("ycc_to_rgb_blocks needs a multiple of 192 ciphertexts");
+    const size_t ctw = 2 * s.poly_words();
+    detail::DevBuf buf(data.size() * ctw);
+    for (size_t i = 0; i < data.size(); ++i) {
+        if (data[i].size() != 2) throw std::invalid_argument("ycc_to_rgb_blocks needs size-2 ciphertexts");
+        detail::check(fhe_copy(buf.ptr() + i * ctw, data[i].ptr(), ctw * 8, nullptr), "copy");
+    }
+    detail::check(fhe_ycc_to_rgb_blocks(s.h, buf.ptr(), data.size() / 192, int_coeffs, frac_coeffs, nullptr), "ycc_to_rgb_blocks");
+    for (size_t i = 0; i < data.size(); ++i) detail::check(fhe_copy(data[i].ptr(), buf.ptr() + i * ctw, ctw * 8, nullptr), "copy");
+    detail::check(fhe_stream_sync(nullptr), "sync");
+}
 }  // namespace hip
 
 }  // namespace seal

@@ -19,7 +19,7 @@ import struct
 import numpy as np
 import torch
 
-from .evaluator import DctPlan, Evaluator
+from .evaluator import DctPlan, Evaluator, IdctPlan
 
 MAGIC = b"FHEHIP1\x00"
 HEADER = struct.Struct("<8sIIII")
@@ -235,11 +235,40 @@ def server_jpeg(ctx, in_path, out_path, n_blocks, wave_blocks=8, quant=None, do_
     stats (a dict), if given, receives wall seconds, device compute seconds and byte counts.
     validate: every uploaded wave is checked for residues that are not below their modulus (fhe_count_unreduced; ValueError at
     the end of the job -- what Ciphertext::load rejects per ciphertext, homo/server_jpeg.cpp:117-123)."""
+    ev = Evaluator(ctx)
+    plan = DctPlan(ctx, quant) if do_dct else None
+
+    def compute(din, dout, nb):
+        ev.rgb_to_ycc_blocks(din)                                # in place: Y, Cb, Cr in the stream's block layout
+        if do_dct:
+            ev.dct8x8_quant(plan, din.view(nb * 3, 64, 2, ctx.k, ctx.n), out=dout.view(nb * 3, 64, 2, ctx.k, ctx.n))
+
+    return _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, do_dct, io_threads, slots, stats, validate)
+
+
+def server_jpeg_decompress(ctx, in_path, out_path, n_blocks, quant=None, to_rgb=True, wave_blocks=8, io_threads=8, slots=3, stats=None, validate=True):
+    """The way back: reads what server_jpeg writes (per block 64 Y, 64 Cb, 64 Cr ciphertexts of quantised DCT coefficients) and
+    writes what server_jpeg reads (per block 64 R, 64 G, 64 B).  Per wave: fhe_idct8x8_dequant over the 3 * wave channel-blocks
+    (dequantisation by `quant`, None: skipped -- pass the table server_jpeg quantised with), then, with to_rgb, fhe_ycc_to_rgb_blocks in
+    place on the stream layout.  Same five-stage pipeline, arguments and residue validation as server_jpeg.  Returns blocks processed.
+    A server_jpeg + server_jpeg_decompress round trip decrypts to the pixels only with a plain modulus t >= 2^26 (include/fhe_hip.h)."""
+    ev = Evaluator(ctx)
+    plan = IdctPlan(ctx, quant)
+
+    def compute(din, dout, nb):
+        ev.idct8x8_dequant(plan, din.view(nb * 3, 64, 2, ctx.k, ctx.n), out=dout.view(nb * 3, 64, 2, ctx.k, ctx.n))
+        if to_rgb:
+            ev.ycc_to_rgb_blocks(dout)                           # in place: R, G, B in the stream's block layout
+
+    return _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, True, io_threads, slots, stats, validate)
+
+
+def _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, separate_out, io_threads, slots, stats, validate):
+    """server_jpeg's pipeline over records of 192 ciphertexts per block; compute(din, dout, nb) runs on the main stream for one wave
+    (din is dout unless separate_out)."""
     import queue
     import threading
     import time
-    ev = Evaluator(ctx)
-    plan = DctPlan(ctx, quant) if do_dct else None
     residues = _ResidueCheck(ctx, validate)
     wave_blocks = max(1, min(wave_blocks, n_blocks))
     slots = max(2, slots)
@@ -247,7 +276,7 @@ def server_jpeg(ctx, in_path, out_path, n_blocks, wave_blocks=8, quant=None, do_
     hin = [_pinned(("in", i), shape) for i in range(slots)]
     hout = [_pinned(("out", i), shape) for i in range(slots)]
     din = [torch.empty(shape, dtype=torch.int64, device=ctx.device) for _ in range(2)]
-    dout = [torch.empty(shape, dtype=torch.int64, device=ctx.device) for _ in range(2)] if do_dct else din
+    dout = [torch.empty(shape, dtype=torch.int64, device=ctx.device) for _ in range(2)] if separate_out else din
     main = torch.cuda.current_stream()
     h2d, d2h = _copy_streams()
     rec = RECORD_HEADER + 2 * ctx.k * ctx.n * 8
@@ -340,9 +369,7 @@ def server_jpeg(ctx, in_path, out_path, n_blocks, wave_blocks=8, quant=None, do_
                 t_start.append(torch.cuda.Event(enable_timing=True))
                 t_start[-1].record(main)
             residues.add(din[d][:nb])
-            ev.rgb_to_ycc_blocks(din[d][:nb])                    # in place: Y, Cb, Cr in the stream's block layout
-            if do_dct:
-                ev.dct8x8_quant(plan, din[d][:nb].view(nb * 3, 64, 2, ctx.k, ctx.n), out=dout[d][:nb].view(nb * 3, 64, 2, ctx.k, ctx.n))
+            compute(din[d][:nb], dout[d][:nb], nb)
             if stats is not None:
                 t_stop.append(torch.cuda.Event(enable_timing=True))
                 t_stop[-1].record(main)

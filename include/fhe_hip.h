@@ -77,7 +77,9 @@ const char *fhe_last_error(void);
  *      fhe_decrypt_batch / fhe_decrypt_scratch_bytes / fhe_ctx_modulus_bits.
  *   4: + fhe_relinearize_poly / fhe_relinearize_n (key switches for s^3 ..: a size-4 Cubic result goes to size 2 in one
  *      evaluator.relinearize, as SEAL's does), fhe_circuits_create_relin_at (include/fhe_circuits.h: where the relinearised mode
- *      relinearises); fhe_relinearize_to rejects partially overlapping input / output ranges.
+ *      relinearises); fhe_relinearize_to rejects partially overlapping input / output ranges.  Version 4 also carries
+ *      fhe_idct_plan_create / destroy, fhe_idct8x8_scratch_bytes, fhe_idct8x8_dequant and fhe_ycc_to_rgb_blocks, added later:
+ *      new entry points only, no existing signature or contract changed.
  * A host compiled against this header compares fhe_abi_version() with FHE_ABI_VERSION before anything else (the Python
  * binding and seal/seal.h do). */
 #define FHE_ABI_VERSION 4
@@ -311,6 +313,45 @@ int fhe_rgb_to_ycc(const fhe_ctx *ctx, uint64_t *r, uint64_t *g, uint64_t *b, ui
  * 64 B ciphertexts): blocks [n_blocks][3][64][2][k][n], in place -> [n_blocks][Y, Cb, Cr][64][2][k][n], which read as
  * [3 n_blocks][64][2][k][n] is the input layout of fhe_dct8x8_quant and the order homo/server_jpeg.cpp:146-153 saves. */
 int fhe_rgb_to_ycc_blocks(const fhe_ctx *ctx, uint64_t *blocks, uint64_t n_blocks, int int_coeffs, int frac_coeffs,
+                          fhe_stream stream);
+
+/* ---- the way back: dequantisation + 8x8 inverse DCT, and YCbCr -> RGB ------------------------------
+ * fhe_idct8x8_dequant runs, on n_blocks independent 8x8 blocks of 64 size-2 ciphertexts c[0..63] (row-major),
+ *     1. c[i] = multiply_plain(c[i], encode(Q[i]))          (skipped for a plan built with quant64 == NULL)
+ *     2. idct_line(c[8r .. 8r+7]) for every row r
+ *     3. idct_line(c[col], c[col+8], ..., c[col+56]) for every column col
+ *     4. c[i] = multiply_plain(c[i], encode(0.125))
+ * with encode = FractionalEncoder(int_coeffs, frac_coeffs) and idct_line the transpose of encrypted_dct's LL&M line
+ * (IJG jidctint, the same twelve constants; A = add, S = sub, M = multiply_plain):
+ *     z1 = M(A(d2, d6), .541196100);  t2 = A(z1, M(d6, -1.847759065));  t3 = A(z1, M(d2, .765366865))
+ *     t0 = A(d0, d4);  t1 = S(d0, d4);  t10 = A(t0, t3);  t13 = S(t0, t3);  t11 = A(t1, t2);  t12 = S(t1, t2)
+ *     u0, u1, u2, u3 = d7, d5, d3, d1;  z1 = A(u0, u3);  z2 = A(u1, u2);  z3 = A(u0, u2);  z4 = A(u1, u3)
+ *     z5 = M(A(z3, z4), 1.175875602)
+ *     u0 = M(u0, .298631336);  u1 = M(u1, 2.053119869);  u2 = M(u2, 3.072711026);  u3 = M(u3, 1.501321110)
+ *     z1 = M(z1, -.899976223);  z2 = M(z2, -2.562915447)
+ *     z3 = A(M(z3, -1.961570560), z5);  z4 = A(M(z4, -.390180644), z5)
+ *     u0 = A(u0, A(z1, z3));  u1 = A(u1, A(z2, z4));  u2 = A(u2, A(z2, z3));  u3 = A(u3, A(z1, z4))
+ *     out = [A(t10,u3), A(t11,u2), A(t12,u1), A(t13,u0), S(t13,u0), S(t12,u1), S(t11,u2), S(t10,u3)]
+ * The result is bit-identical to that op-by-op sequence (steps 1 and 4 are applied as one product with the ring element
+ * encode(Q[i]) * encode(0.125)).  in/out: [n_blocks][64][2][k][n]; out may alias in; n_blocks == 0 is a no-op; a zero
+ * quant64[i] is refused.  Kernels as fhe_dct_path says: 1 = the fused exact-FP64 pair k_idct_rows + k_idct_cols, otherwise
+ * k_ntt_fwd + k_idct_slots / k_idct_lines_pm + k_ntt_inv.  scratch: fhe_idct8x8_scratch_bytes (the fused pair's wave
+ * intermediate, as fhe_dct8x8_quant's; 0 where the general path runs).
+ * Plaintext growth: after fhe_dct8x8_quant, the chained products of fractional encodings pass t = 2^14 and wrap (the
+ * decrypted pixels are wrong although the noise budget is large); a forward + inverse round trip needs t >= 2^22, and
+ * t >= 2^26 with the colour conversion on both sides (rgb_to_ycc ... ycc_to_rgb). */
+typedef struct fhe_idct_plan fhe_idct_plan;
+int fhe_idct_plan_create(const fhe_ctx *ctx, const double *quant64, int int_coeffs, int frac_coeffs, fhe_stream stream,
+                         fhe_idct_plan **out);
+int fhe_idct_plan_destroy(fhe_idct_plan *plan);
+size_t fhe_idct8x8_scratch_bytes(const fhe_ctx *ctx, uint64_t n_blocks);
+int fhe_idct8x8_dequant(const fhe_ctx *ctx, const fhe_idct_plan *plan, const uint64_t *in, uint64_t *out,
+                        uint64_t n_blocks, void *scratch, size_t scratch_bytes, fhe_stream stream);
+/* JFIF YCbCr -> RGB, the inverse of rgb_to_ycc_fhe, on the stream layout: blocks [n_blocks][Y, Cb, Cr][64][2][k][n], in
+ * place -> [n_blocks][R, G, B][64][2][k][n] (fhe_rgb_to_ycc_blocks' input layout):
+ *     Y' = add_plain(Y, encode(128.0));  R = A(Y', M(Cr, 1.402));  G = S(S(Y', M(Cb, .344136)), M(Cr, .714136));  B = A(Y', M(Cb, 1.772))
+ * bit-identical to that sequence; n_blocks == 0 is a no-op. */
+int fhe_ycc_to_rgb_blocks(const fhe_ctx *ctx, uint64_t *blocks, uint64_t n_blocks, int int_coeffs, int frac_coeffs,
                           fhe_stream stream);
 
 /* ---- server-side encryptions (round 5) ------------------------------------------------------------
