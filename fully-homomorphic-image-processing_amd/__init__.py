@@ -8,8 +8,9 @@ or through the `fhip_amd` shim at the repository root.
 from . import _lib, circuits, client, parallel, server
 from ._lib import FheError, LIB_PATH, HEADER_PATH, HEADER_PATHS
 from .keys import Decryptor, DeviceEncryptor, Encryptor, KeyGenerator
-from .evaluator import (PRESETS, SEED, YQT, DctPlan, Evaluator, FractionalEncoder, IdctPlan, PreparedPlain, SEALContext,
+from .circuits import FILTERS, filter_source_rows, filter_tap_plan
+from .evaluator import (FILTER_MAX_TAPS, PRESETS, SEED, YQT, DctPlan, Evaluator, FilterPlan, FractionalEncoder, IdctPlan, PreparedPlain, SEALContext,
                         to_device, to_host)
 
-__all__ = ["KeyGenerator", "Encryptor", "DeviceEncryptor", "Decryptor", "FheError", "LIB_PATH", "HEADER_PATH", "HEADER_PATHS", "PRESETS", "SEED", "YQT", "DctPlan", "IdctPlan", "Evaluator",
-           "FractionalEncoder", "PreparedPlain", "SEALContext", "to_device", "to_host", "_lib", "parallel", "circuits", "server", "client"]
+__all__ = ["KeyGenerator", "Encryptor", "DeviceEncryptor", "Decryptor", "FheError", "LIB_PATH", "HEADER_PATH", "HEADER_PATHS", "PRESETS", "SEED", "YQT", "DctPlan", "IdctPlan", "FilterPlan", "Evaluator",
+           "FractionalEncoder", "PreparedPlain", "SEALContext", "to_device", "to_host", "_lib", "parallel", "circuits", "server", "client", "FILTERS", "FILTER_MAX_TAPS", "filter_tap_plan", "filter_source_rows"]

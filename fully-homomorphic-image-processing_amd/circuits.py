@@ -266,6 +266,63 @@ def sample_linear(ev, pc, pixels, taps, xfract, yfract, relin=None):
     return _sample("fhe_sample_linear", 4, SAMPLE_LINEAR, ev, pc, pixels, taps, xfract, yfract, relin)
 
 
+# ------------------------------------------------------------------------------------------------
+# 2-D convolution filters (Evaluator.filter2d / fhe_filter2d)
+# ------------------------------------------------------------------------------------------------
+def _filter(weights, anchor=None, stride=(1, 1)):
+    w = np.array(weights, dtype=np.float64)
+    return dict(weights=w, anchor=filter_anchor(w.shape[1], w.shape[0]) if anchor is None else anchor, stride=stride)
+
+
+def filter_anchor(kw, kh):
+    """default anchor of a kw x kh kernel: its centre, the upper-left of the four central positions for even extents"""
+    return ((kw - 1) // 2, (kh - 1) // 2)
+
+
+# named kernels: weights [kh][kw], anchor (x, y), stride (x, y)
+FILTERS = {
+    "box3": _filter(np.full((3, 3), 1.0 / 9.0)),
+    "gauss3": _filter(np.outer([1, 2, 1], [1, 2, 1]) / 16.0),
+    "gauss5": _filter(np.outer([1, 4, 6, 4, 1], [1, 4, 6, 4, 1]) / 256.0),
+    "sobel_x": _filter([[-1, 0, 1], [-2, 0, 2], [-1, 0, 1]]),
+    "sobel_y": _filter([[-1, -2, -1], [0, 0, 0], [1, 2, 1]]),
+    "laplace": _filter([[0, 1, 0], [1, -4, 1], [0, 1, 0]]),
+    "sharpen": _filter([[0, -1, 0], [-1, 5, -1], [0, -1, 0]]),
+    "chroma420": _filter(np.full((2, 2), 0.25), anchor=(0, 0), stride=(2, 2)),      # the 2x2 average of 4:2:0 chroma subsampling
+}
+
+
+def filter_tap_plan(src_w, src_h, kw, kh, channels=1, anchor=None, stride=(1, 1), rows=None, src_row0=None, taps=True):
+    """Index arithmetic of a kw x kh filter with clamp-to-edge borders (fhe_filter_tap_plan): returns (taps, dst_w, dst_h), taps a
+    uint32 array [(row1 - row0) * dst_w * channels][kw * kh] of record indices for destination rows `rows` (default: all), relative to a
+    resident window that starts at source row `src_row0` (default: the first row those destination rows read).  Record of pixel
+    (x, y), channel c: (y * src_w + x) * channels + c; outputs in the same interleaved order.  taps=False only reports the sizes."""
+    ax, ay = filter_anchor(kw, kh) if anchor is None else anchor
+    sx, sy = stride
+    dw, dh = C.c_uint32(), C.c_uint32()
+    _lib.call("fhe_filter_tap_plan", src_w, src_h, channels, kw, kh, ax, ay, sx, sy, 0, 0, 0, C.byref(dw), C.byref(dh), None)
+    dst_w, dst_h = int(dw.value), int(dh.value)
+    if not taps:
+        return None, dst_w, dst_h
+    row0, row1 = (0, dst_h) if rows is None else (int(rows[0]), int(rows[1]))
+    if not (0 <= row0 < row1 <= dst_h):
+        raise ValueError("rows %r are not a range of the %d destination rows" % (rows, dst_h))
+    if src_row0 is None:
+        src_row0 = filter_source_rows(src_h, kh, ay, sy, row0, row1)[0]
+    out = np.zeros(((row1 - row0) * dst_w * channels, kw * kh), dtype=np.uint32)
+    _lib.call("fhe_filter_tap_plan", src_w, src_h, channels, kw, kh, ax, ay, sx, sy, row0, row1, int(src_row0), C.byref(dw), C.byref(dh),
+              out.ctypes.data_as(C.c_void_p))
+    return out, dst_w, dst_h
+
+
+def filter_source_rows(src_h, kh, anchor_y, stride_y, row0, row1):
+    """(first, count) of the source rows destination rows [row0, row1) of a filter read (fhe_filter_source_rows): the rows plus the halo,
+    clamped -- what a GPU that owns those destination rows has to load."""
+    first, count = C.c_uint32(), C.c_uint32()
+    _lib.call("fhe_filter_source_rows", src_h, kh, anchor_y, stride_y, row0, row1, C.byref(first), C.byref(count))
+    return int(first.value), int(count.value)
+
+
 BAND_CONSUMER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p)
 
 

@@ -67,6 +67,7 @@ struct FheOptions {
     bool relin_steps = false;        // FHE_RELIN_STEPS=1: fhe_relinearize_n runs its key switches one after the other (round 6: the default folds them into one pass, behz.hip relin_pm)
     bool relin_fused = false;        // FHE_RELIN_FUSED=1 (experiment, round 5): key-switch accumulation inside the inverse-transform kernel (k_relin_accum_inv_add_pm: one launch and
                                      // 4 MB of traffic per relinearisation less, same bits, 1-3 % SLOWER at dbc = 30 -- the digits are read twice and the kernels are issue-bound; profiles/EXPERIMENTS.md)
+    bool filter_xcd = true;          // FHE_FILTER_XCD=0: fhe_filter2d hands its workgroups out in plain order (every eighth output per XCD) instead of one contiguous run of outputs per XCD
     bool behz_fused_prepare = false; // FHE_BEHZ_FUSED_PREPARE=1: base extension fused into the forward transforms (k_behz_prepare_pm: 25 % less HBM traffic per
                                      // product, 5 % slower -- the y_i are recomputed per auxiliary prime and the kernels are issue-bound; profiles/EXPERIMENTS.md)
 };

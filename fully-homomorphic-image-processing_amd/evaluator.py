@@ -248,6 +248,40 @@ class IdctPlan:
             self.h = None
 
 
+FILTER_MAX_TAPS = 64       # FHE_FILTER_MAX_TAPS in include/fhe_hip.h
+
+
+class FilterPlan:
+    """Constants of fhe_filter2d: a 2-D convolution kernel of public weights ([kh][kw], row-major), each distinct weight encoded
+    (FractionalEncoder(int_coeffs, frac_coeffs)), lifted and transformed once.  Positions whose weight encodes to zero are skipped."""
+
+    def __init__(self, ctx, weights, int_coeffs=100, frac_coeffs=100):
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.ndim != 2 or w.size == 0:
+            raise ValueError("FilterPlan: weights must be a non-empty 2-D array [kh][kw], got shape %r" % (w.shape,))
+        if w.size > FILTER_MAX_TAPS:
+            raise ValueError("FilterPlan: %d x %d kernel positions, at most FHE_FILTER_MAX_TAPS = %d" % (w.shape[1], w.shape[0], FILTER_MAX_TAPS))
+        if not np.all(np.isfinite(w)):
+            raise ValueError("FilterPlan: weights must be finite")
+        if not np.any(w != 0.0):
+            raise ValueError("FilterPlan: every weight is zero (multiply_plain by the zero plaintext is refused)")
+        self.ctx, self.weights = ctx, w
+        self.kh, self.kw = int(w.shape[0]), int(w.shape[1])
+        h = C.c_void_p()
+        _lib.call("fhe_filter_plan_create", ctx.h, w.ctypes.data_as(C.c_void_p), self.kw, self.kh, int_coeffs, frac_coeffs, _stream(), C.byref(h))
+        self.h = h
+        self.taps = int(_lib.call("fhe_filter_plan_taps", h))      # positions whose weight does not encode to zero
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h:
+            try:
+                _lib.load().fhe_filter_plan_destroy(h)
+            except Exception:
+                pass
+            self.h = None
+
+
 def check_evaluation_keys(ctx, evk_ntt, dbc, need, who):
     """The library takes the keys as a bare pointer and reads need * fhe_evk_words(ctx, dbc) words behind it (include/fhe_hip.h): the host
     checks that the tensor it hands over holds them -- a key tensor made for another decomposition bit count (fewer digits), another context or
@@ -528,3 +562,43 @@ class Evaluator:
         n_blocks = blocks.numel() // (3 * 64 * 2 * self.ctx.k * self.ctx.n)
         _lib.call("fhe_ycc_to_rgb_blocks", self.ctx.h, _ptr(blocks), n_blocks, int_coeffs, frac_coeffs, _stream())
         return blocks
+
+    def filter2d(self, plan, src, taps, out=None, src_is_ntt=False):
+        """2-D convolution with public weights (fhe_filter2d, include/fhe_hip.h): output c = the sum over the kernel positions p of
+        multiply_plain(src[taps[c][p]], encode(w[p])), bit for bit the op-by-op composition, with one forward transform per source
+        and one inverse transform per output.  src: [n_src, size, k, n] (never written); taps: [count][kw * kh] indices into src
+        (circuits.filter_tap_plan); returns [count, size, k, n].  src_is_ntt: src already is ntt_forward of the ciphertexts."""
+        kn = (self.ctx.k, self.ctx.n)
+        if not (isinstance(src, torch.Tensor) and src.dim() >= 4 and tuple(src.shape[-2:]) == kn and src.dtype == torch.int64 and src.is_contiguous()
+                and src.device == self.ctx.device and src.shape[-3] >= 1):
+            raise ValueError("filter2d: `src` must be a contiguous int64 tensor [..., size, k, n] = [..., size, %d, %d] on the context's device, got %r"
+                             % (kn + (tuple(getattr(src, "shape", ())),)))
+        if plan.ctx is not self.ctx:
+            raise ValueError("filter2d: the plan was built for another context")
+        size = int(src.shape[-3])
+        n_src = src.numel() // (size * kn[0] * kn[1])
+        width = plan.kw * plan.kh
+        t = np.asarray(taps)
+        if t.ndim != 2 or t.shape[1] != width or t.dtype.kind not in "iu":
+            raise ValueError("filter2d: `taps` must be an integer array [count][kw * kh = %d], got shape %r dtype %s" % (width, t.shape, t.dtype))
+        if t.size and (int(t.min()) < 0 or int(t.max()) >= n_src):
+            raise ValueError("filter2d: taps must index the %d source ciphertexts, got values in [%d, %d]" % (n_src, int(t.min()), int(t.max())))
+        t = np.ascontiguousarray(t, dtype=np.uint32)
+        count = int(t.shape[0])
+        shape = (count, size) + kn
+        if out is not None:
+            if not (isinstance(out, torch.Tensor) and tuple(out.shape) == shape and out.dtype == torch.int64 and out.is_contiguous() and out.device == src.device):
+                raise ValueError("filter2d: `out` must be a contiguous int64 tensor %r on the device of `src`, got %r" % (shape, tuple(getattr(out, "shape", ()))))
+            a0, a1 = src.data_ptr(), src.data_ptr() + src.numel() * 8
+            b0, b1 = out.data_ptr(), out.data_ptr() + out.numel() * 8
+            if out.numel() and a0 < b1 and b0 < a1:
+                raise ValueError("filter2d: `out` overlaps `src`")
+        else:
+            out = torch.empty(shape, dtype=torch.int64, device=src.device)
+        if count == 0:
+            return out
+        nbytes = _lib.load().fhe_filter2d_scratch_bytes(self.ctx.h, plan.h, size, n_src, count, int(bool(src_is_ntt)))
+        scr = self._scratch_buf(nbytes)
+        _lib.call("fhe_filter2d", self.ctx.h, plan.h, _ptr(src), n_src, size, int(bool(src_is_ntt)), t.ctypes.data_as(C.c_void_p), _ptr(out), count,
+                  _ptr(scr), nbytes, _stream())
+        return out

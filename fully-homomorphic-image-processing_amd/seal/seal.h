@@ -1622,6 +1622,40 @@ inline void ycc_to_rgb_blocks(const SEALContext &ctx, std::vector<Ciphertext> &d
     for (size_t i = 0; i < data.size(); ++i) detail::check(fhe_copy(data[i].ptr(), buf.ptr() + i * ctw, ctw * 8, nullptr), "copy");
     detail::check(fhe_stream_sync(nullptr), "sync");
 }
+// 2-D convolution with public weights (fhe_filter2d, include/fhe_hip.h): out[c] = sum over the kernel positions p of
+// multiply_plain(src[taps[c * kw * kh + p]], encode(weights[p])), positions whose weight encodes to zero skipped -- bit for bit the
+// Evaluator calls, with one transform per source and one per output.  weights: [kh][kw] row-major; taps: [count][kw * kh] indices
+// into src (fhe_filter_tap_plan builds them for an image with clamp-to-edge borders).  All sources have one size.
+inline std::vector<Ciphertext> filter2d(const SEALContext &ctx, const std::vector<Ciphertext> &src, const std::vector<double> &weights, uint32_t kw,
+                                        uint32_t kh, const std::vector<uint32_t> &taps, int int_coeffs = 100, int frac_coeffs = 100) {
+    const detail::CtxState &s = *ctx.state();
+    const size_t np = (size_t)kw * kh;
+    if (src.empty()) throw std::invalid_argument("filter2d needs source ciphertexts");
+    if (!np || weights.size() != np) throw std::invalid_argument("filter2d needs kw * kh weights");
+    if (taps.size() % np) throw std::invalid_argument("filter2d needs kw * kh taps per output");
+    const size_t count = taps.size() / np;
+    const int size = src[0].size();
+    const size_t ctw = (size_t)size * s.poly_words();
+    detail::DevBuf in(src.size() * ctw), out((count ? count : 1) * ctw);
+    for (size_t i = 0; i < src.size(); ++i) {
+        if (src[i].size() != size) throw std::invalid_argument("filter2d needs sources of one size");
+        detail::check(fhe_copy(in.ptr() + i * ctw, src[i].ptr(), ctw * 8, nullptr), "copy");
+    }
+    fhe_filter_plan *plan = nullptr;
+    detail::check(fhe_filter_plan_create(s.h, weights.data(), kw, kh, int_coeffs, frac_coeffs, nullptr, &plan), "filter plan");
+    const size_t bytes = fhe_filter2d_scratch_bytes(s.h, plan, (uint32_t)size, src.size(), count, 0);
+    detail::DevBuf scratch((bytes + 7) / 8 + 1);
+    int rc = fhe_filter2d(s.h, plan, in.ptr(), src.size(), (uint32_t)size, 0, taps.data(), out.ptr(), count, scratch.ptr(), bytes, nullptr);
+    fhe_filter_plan_destroy(plan);
+    detail::check(rc, "filter2d");
+    std::vector<Ciphertext> res(count);
+    for (size_t i = 0; i < count; ++i) {
+        res[i] = src[0];                                      // the shape; ptr() below detaches the handle (copy on write)
+        detail::check(fhe_copy(res[i].ptr(), out.ptr() + i * ctw, ctw * 8, nullptr), "copy");
+    }
+    detail::check(fhe_stream_sync(nullptr), "sync");
+    return res;
+}
 }  // namespace hip
 
 }  // namespace seal

@@ -19,7 +19,7 @@ import struct
 import numpy as np
 import torch
 
-from .evaluator import DctPlan, Evaluator, IdctPlan
+from .evaluator import DctPlan, Evaluator, FilterPlan, IdctPlan
 
 MAGIC = b"FHEHIP1\x00"
 HEADER = struct.Struct("<8sIIII")
@@ -737,6 +737,101 @@ def server_resize(ctx, in_path, out_path, src_w, src_h, dst_w, dst_h, bicubic, e
         if own_in:
             fin.close()
         if own_out:
+            fout.close()
+    return (row1 - row0) * dst_w
+
+
+# ------------------------------------------------------------------------------------------------
+# server_filter: a 2-D convolution with public weights over a pixel stream
+# ------------------------------------------------------------------------------------------------
+def server_filter(ctx, in_path, out_path, width, height, weights, anchor=None, stride=(1, 1), rows_per_step=4, validate=True, rows=None, io_threads=8,
+                  int_coeffs=100, frac_coeffs=100, stats=None):
+    """Filter an encrypted image with the public kernel `weights` ([kh][kw]; clamp-to-edge borders, circuits.filter_tap_plan).
+
+    Input stream: width * height pixels, row by row, three size-2 records (R, G, B) per pixel -- what client.send_resize writes.
+    Output stream: dst_w * dst_h pixels (dst = ceil(src / stride)) in the same order, three size-2 records per pixel -- what
+    client.receive_pixels reads.  in_path / out_path: file names or open StreamFile objects.  Returns the number of pixels produced.
+
+    A step produces up to `rows_per_step` destination rows, all three channels in ONE Evaluator.filter2d call.  Only the step's source
+    rows and their halo are resident, at most (rows_per_step * stride_y + kh) * width * 3 ciphertexts, kept in NTT form (src_is_ntt):
+    every source row is read from the file once, checked (`validate`: fhe_count_unreduced, as the other servers) and transformed once;
+    the rows the next step reads again are moved to the front of the window (a copy of at most kh rows).  The loop is SYNCHRONOUS: read,
+    upload, compute, download, write, one after the other -- no reader / writer threads as in server_resize.
+
+    rows=(y0, y1) produces a SHARD of the destination rows at the band's own position of the output stream, reading only those rows'
+    source rows (circuits.filter_source_rows): processes with disjoint row ranges fill one output file without any exchange."""
+    import time
+    from . import circuits
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    plan = FilterPlan(ctx, w, int_coeffs, frac_coeffs)
+    kh, kw = plan.kh, plan.kw
+    ax, ay = circuits.filter_anchor(kw, kh) if anchor is None else anchor
+    sx, sy = stride
+    _, dst_w, dst_h = circuits.filter_tap_plan(width, height, kw, kh, channels=3, anchor=(ax, ay), stride=(sx, sy), taps=False)
+    row0, row1 = (0, dst_h) if rows is None else (int(rows[0]), int(rows[1]))
+    if not (0 <= row0 < row1 <= dst_h):
+        raise ValueError("rows %r are not a range of the %d destination rows" % (rows, dst_h))
+    if rows_per_step < 1:
+        raise ValueError("rows_per_step must be positive")
+    ev = Evaluator(ctx)
+    residues = _ResidueCheck(ctx, validate)
+    rec = RECORD_HEADER + 2 * ctx.k * ctx.n * 8
+    own_in, own_out = not isinstance(in_path, StreamFile), not isinstance(out_path, StreamFile)
+    if (in_path.size if not own_in else os.path.getsize(in_path)) < width * height * 3 * rec:
+        raise EOFError("ciphertext stream ended")
+    steps = [(y, min(y + rows_per_step, row1)) for y in range(row0, row1, rows_per_step)]
+    spans = [circuits.filter_source_rows(height, kh, ay, sy, a, b) for a, b in steps]       # (first, count) per step
+    max_rows = max(c for _, c in spans)
+    assert max_rows <= rows_per_step * sy + kh
+    shape = (2, ctx.k, ctx.n)
+    resident = torch.empty((max_rows, width, 3) + shape, dtype=torch.int64, device=ctx.device)     # NTT form, source rows [lo, hi)
+    fresh = torch.empty((max_rows, width, 3) + shape, dtype=torch.int64, device=ctx.device)        # a step's new rows as uploaded
+    hin = _pinned(("flt_in",), (max_rows, width, 3) + shape)
+    max_px = rows_per_step * dst_w
+    hout = _pinned(("flt_out",), (max_px, 3) + shape)
+    dout = torch.empty((max_px, 3) + shape, dtype=torch.int64, device=ctx.device)
+    fin = StreamFile(in_path) if own_in else in_path
+    fout = None
+    t0, seconds = time.perf_counter(), {"read": 0.0, "write": 0.0}
+    try:
+        fout = StreamFile(out_path, write=True, size=dst_w * dst_h * 3 * rec) if own_out else out_path
+        if fout.size < dst_w * dst_h * 3 * rec:
+            raise ValueError("output stream file is smaller than the result")
+        lo = hi = spans[0][0]                                                                # resident source rows [lo, hi)
+        for (y0, y1), (first, cnt) in zip(steps, spans):
+            keep_from = min(max(first, lo), hi)
+            keep = hi - keep_from
+            if keep and keep_from > lo:
+                resident[:keep].copy_(resident[keep_from - lo:hi - lo].clone())
+            lo = first if keep == 0 else keep_from
+            new_first, new_cnt = lo + keep, first + cnt - (lo + keep)
+            if new_cnt > 0:
+                t_io = time.perf_counter()
+                fin.transfer(new_first * width * 3, new_cnt * width * 3, 2, ctx, hin, io_threads)
+                seconds["read"] += time.perf_counter() - t_io
+                fresh[:new_cnt].copy_(hin[:new_cnt], non_blocking=True)
+                residues.add(fresh[:new_cnt])
+                ev.ntt_forward(fresh[:new_cnt], out=resident[keep:keep + new_cnt])
+            hi = first + cnt
+            assert lo == first and hi - lo <= max_rows
+            taps, _, _ = circuits.filter_tap_plan(width, height, kw, kh, channels=3, anchor=(ax, ay), stride=(sx, sy), rows=(y0, y1), src_row0=lo)
+            npx = (y1 - y0) * dst_w
+            src = resident[:hi - lo].view(-1, *shape)
+            ev.filter2d(plan, src, taps, out=dout[:npx].view(-1, *shape), src_is_ntt=True)
+            hout[:npx].copy_(dout[:npx], non_blocking=True)
+            torch.cuda.current_stream().synchronize()                                        # hin may be refilled, hout has landed
+            t_io = time.perf_counter()
+            fout.transfer(y0 * dst_w * 3, npx * 3, 2, ctx, hout, io_threads)
+            seconds["write"] += time.perf_counter() - t_io
+        residues.verdict(_refuser(own_out, fout, out_path))
+        if stats is not None:
+            stats.update(seconds=time.perf_counter() - t0, steps=len(steps), file_read_seconds=seconds["read"], file_write_seconds=seconds["write"],
+                         resident_rows=max_rows, dst_w=dst_w, dst_h=dst_h)
+    finally:
+        torch.cuda.synchronize()
+        if own_in:
+            fin.close()
+        if own_out and fout is not None:
             fout.close()
     return (row1 - row0) * dst_w
 

@@ -79,7 +79,7 @@ const char *fhe_last_error(void);
  *      evaluator.relinearize, as SEAL's does), fhe_circuits_create_relin_at (include/fhe_circuits.h: where the relinearised mode
  *      relinearises); fhe_relinearize_to rejects partially overlapping input / output ranges.  Version 4 also carries
  *      fhe_idct_plan_create / destroy, fhe_idct8x8_scratch_bytes, fhe_idct8x8_dequant and fhe_ycc_to_rgb_blocks, added later:
- *      new entry points only, no existing signature or contract changed.
+ *      new entry points only, no existing signature or contract changed.  The same holds for the fhe_filter_* entry points (2-D convolution).
  * A host compiled against this header compares fhe_abi_version() with FHE_ABI_VERSION before anything else (the Python
  * binding and seal/seal.h do). */
 #define FHE_ABI_VERSION 4
@@ -353,6 +353,60 @@ int fhe_idct8x8_dequant(const fhe_ctx *ctx, const fhe_idct_plan *plan, const uin
  * bit-identical to that sequence; n_blocks == 0 is a no-op. */
 int fhe_ycc_to_rgb_blocks(const fhe_ctx *ctx, uint64_t *blocks, uint64_t n_blocks, int int_coeffs, int frac_coeffs,
                           fhe_stream stream);
+
+/* ---- 2-D convolution filters with public weights on encrypted pixels --------------------------------
+ * Blur, sharpen, Sobel / Laplacian, the 2x2 average of 4:2:0 chroma subsampling: out[y][x] = sum_j,i w[j][i] * src[y sy + j - ay][x sx + i - ax]
+ * on the per-pixel ciphertexts of the resize and decode streams.  Specification of ONE output ciphertext with tap indices
+ * tap[0 .. kw*kh) (row-major over the kernel, x fastest) into a batch of source ciphertexts of `size` polynomials each:
+ *     acc = none
+ *     for p in 0 .. kw*kh - 1, in this order:
+ *         if encode(w[p]) is the zero plaintext: continue         (SEAL 2.3 refuses multiply_plain by zero, and so does seal/seal.h)
+ *         term = multiply_plain(src[tap[p]], encode(w[p]))        (encode = FractionalEncoder(int_coeffs, frac_coeffs, base 2))
+ *         acc  = term if acc is none else add(acc, term)
+ *     out = acc                                                   (`size` polynomials, fully reduced)
+ * fhe_filter2d gives exactly these bits with ONE forward transform per source polynomial and ONE inverse transform per output
+ * polynomial (csrc/filter.hip); taps that share a weight are summed before the product.  A kernel whose weights all encode to
+ * zero, or a weight the encoder cannot hold, is refused by fhe_filter_plan_create.  Plaintext products only: no auxiliary base,
+ * the ciphertext size stays what it was, every context fhe_ctx_create accepts is supported.
+ *
+ * Index arithmetic (host only; clamp-to-edge, the convention of fhe_resize_sample_plan): dst_w = ceil(src_w / stride_x),
+ * dst_h = ceil(src_h / stride_y); output (x, y) reads source (clamp(x stride_x + i - anchor_x, 0, src_w - 1),
+ * clamp(y stride_y + j - anchor_y, 0, src_h - 1)) for kernel position (i, j).  Streams interleave `channels` records per pixel: pixel
+ * (x, y), channel c is record (y src_w + x) channels + c, and outputs come in the same interleaved order. */
+#define FHE_FILTER_MAX_TAPS 64     /* kw * kh at most (7x7 and 8x8 kernels fit) */
+typedef struct fhe_filter_plan fhe_filter_plan;
+/* weights: [kh][kw] host doubles.  Each DISTINCT weight is encoded, lifted and transformed once and kept on the device. */
+int fhe_filter_plan_create(const fhe_ctx *ctx, const double *weights, uint32_t kw, uint32_t kh, int int_coeffs, int frac_coeffs,
+                           fhe_stream stream, fhe_filter_plan **out);
+int fhe_filter_plan_destroy(fhe_filter_plan *plan);
+/* number of kernel positions whose weight does not encode to zero */
+int fhe_filter_plan_taps(const fhe_filter_plan *plan);
+/* Host only, no context.  Writes [(row1 - row0) * dst_w * channels][kw * kh] record indices for destination rows [row0, row1), relative to
+ * a resident window of source records that starts at source row src_row0 (which must not lie beyond the first row the shard
+ * reads).  taps == NULL only reports dst_w and dst_h (the row arguments are then ignored).  0 <= anchor < kernel extent. */
+int fhe_filter_tap_plan(uint32_t src_w, uint32_t src_h, uint32_t channels, uint32_t kw, uint32_t kh, int anchor_x, int anchor_y,
+                        uint32_t stride_x, uint32_t stride_y, uint32_t row0, uint32_t row1, uint32_t src_row0, uint32_t *dst_w,
+                        uint32_t *dst_h, uint32_t *taps);
+/* The source rows destination rows [row0, row1) read (their own rows plus the halo, clamped): the counterpart of
+ * fhe_resize_source_rows.  Destination rows are independent, so this is the multi-GPU partition: each device loads its rows plus
+ * the halo and nothing is exchanged. */
+int fhe_filter_source_rows(uint32_t src_h, uint32_t kh, int anchor_y, uint32_t stride_y, uint32_t row0, uint32_t row1, uint32_t *first,
+                           uint32_t *count);
+/* src: [n_src][size][k][n] device memory, never written.  out: [count][size][k][n], must not overlap src.  taps: HOST memory,
+ * [count][kw * kh], consumed before the call returns.  src_is_ntt != 0: src already holds what fhe_ntt_forward writes (canonical
+ * values), no forward pass runs and no scratch is needed -- a streaming server keeps its resident rows transformed and pays the
+ * forward transform once per source row, not once per band.  Otherwise scratch holds the transformed sources
+ * (fhe_filter2d_scratch_bytes = n_src * size * k * n * 8).  Everything is checked before anything is enqueued (a tap >= n_src,
+ * size == 0, a plan of another context, short or overlapping scratch: FHE_ERR_PARAM).  count == 0 is a no-op. */
+size_t fhe_filter2d_scratch_bytes(const fhe_ctx *ctx, const fhe_filter_plan *plan, uint32_t size, uint64_t n_src, uint64_t count,
+                                  int src_is_ntt);
+int fhe_filter2d(const fhe_ctx *ctx, const fhe_filter_plan *plan, const uint64_t *src, uint64_t n_src, uint32_t size, int src_is_ntt,
+                 const uint32_t *taps, uint64_t *out, uint64_t count, void *scratch, size_t scratch_bytes, fhe_stream stream);
+/* which kernels fhe_filter2d launches after the forward transforms (labels in measurements; tests that must know what they ran):
+ * 1 / 2 = k_filter_acc_inv_pm on the pseudo-Mersenne class 1 / 2 of the q-base (gather, lazy sums, products and the inverse transform
+ * in one kernel), 0 = the general path k_filter_mac + fhe_ntt_inverse on Shoup arithmetic, 4 = the general path with the transforms
+ * on the exact-FP64 kernels (where fhe_ntt_forward runs them: n = 4096, primes <= 40 bits). */
+int fhe_filter_path(const fhe_ctx *ctx);
 
 /* ---- server-side encryptions (round 5) ------------------------------------------------------------
  * The reference's servers ENCRYPT inside their loops: SampleLinear / SampleBicubic encrypt frac(x) and frac(y) for every output
