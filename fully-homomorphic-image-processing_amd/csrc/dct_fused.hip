@@ -220,8 +220,11 @@ __device__ __forceinline__ void ntt_inv(double (&x)[M][1 << LE], double (&w)[(1 
 // and the column kernel's first butterfly works on the biased values directly:
 //   t_a - t_b = a - b,   t_a + (t_b - 2 (2^52 + 2^51)) = a + b      (all exact).
 constexpr double PACK_BIAS = 6755399441055744.0;
+// `ob` is the workgroup's uniform base, `vo` the thread's and `so` the uniform byte offset.  This one access keeps a
+// plain pointer: with buffer stores here hipcc spills 45-58 VGPRs of the row kernel in every arrangement tried
+// (profiles/EXPERIMENTS.md section 15), with a __restrict__ pointer none.
 template <int E, int TP>
-__device__ __forceinline__ void store_packed(u64 *__restrict__ o, const double (&x)[E]) {
+__device__ __forceinline__ void store_packed(char *__restrict__ ob, u32 vo, u32 so, const double (&x)[E]) {
     static_assert(E == 8, "packed layout is defined for 8 values per thread");
     u32 lo[8], hi[8];
 #pragma unroll
@@ -231,7 +234,7 @@ __device__ __forceinline__ void store_packed(u64 *__restrict__ o, const double (
         hi[r] = (u32)__double2hiint(t);
     }
 #pragma unroll
-    for (int q = 0; q < 4; q++) o[q * TP] = (u64)lo[2 * q] | ((u64)lo[2 * q + 1] << 32);
+    for (int q = 0; q < 4; q++) *(u64 *)(ob + (size_t)(so + q * TP * 8) + vo) = (u64)lo[2 * q] | ((u64)lo[2 * q + 1] << 32);
     u32 h[2];
 #pragma unroll
     for (int g = 0; g < 2; g++) {
@@ -239,9 +242,9 @@ __device__ __forceinline__ void store_packed(u64 *__restrict__ o, const double (
         const u32 p23 = __builtin_amdgcn_perm(hi[4 * g + 3], hi[4 * g + 2], 0x0c0c0400u);
         h[g] = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
     }
-    o[4 * TP] = (u64)h[0] | ((u64)h[1] << 32);
+    *(u64 *)(ob + (size_t)(so + 4 * TP * 8) + vo) = (u64)h[0] | ((u64)h[1] << 32);
 }
-// Circuit constants through LDS (gfx950 `global_load_lds_dwordx4`): the per-slot constants of a wave -- NT tables x 64
+// Circuit constants through LDS (gfx950 `buffer_load_dwordx4 ... lds`): the per-slot constants of a wave -- NT tables x 64
 // doubles -- are brought straight from L2 into that wave's own LDS region without passing through VGPRs, one slot
 // ahead (two regions per wave, used alternately): the request for slot r+1 is issued before slot r is evaluated, so
 // the L2 round trip that each of the eight per-slot rounds used to expose runs behind the products of the current
@@ -252,17 +255,17 @@ __device__ __forceinline__ void store_packed(u64 *__restrict__ o, const double (
 // table i+1; LDS destination = M0 base + 16 * lane, i.e. table i at doubles [0, 64), table i+1 at [64, 128).
 // (A divergent `if (lane < 32)` for an odd last table would split the basic block, and hipcc then sinks the slots'
 // arithmetic below all eight fetches: 351 spilled VGPRs.)
-typedef __attribute__((address_space(1))) const void lc_gptr;
 typedef __attribute__((address_space(3))) void lc_lptr;
-// `ubase` is wave-uniform (table FIRST of this prime, slot r), `voff` the lane's byte offset: scalar base + 32-bit
-// vector offset keeps the eight slots' addresses out of the VGPRs.
+// `w` is the window of this prime's tables from table FIRST (gwin, fp64_core.h), `soff` the slot's uniform byte offset,
+// `voff` the lane's: `buffer_load_dwordx4 ... lds` takes the three as they are, so the eight slots' addresses never
+// occupy VGPRs (the flat form held a 64-bit pair per request and spilled some of them).
 template <int NT>
-__device__ __forceinline__ void stage_consts(const char *ubase, u32 voff, size_t cstride_bytes, double *stg, int lane) {
+__device__ __forceinline__ void stage_consts(gwin_t w, u32 voff, u32 soff, u32 cstride_bytes, double *stg) {
 #pragma unroll
     for (int i0 = 0; i0 < NT; i0 += 2) {
         const int i = (i0 + 1 < NT) ? i0 : NT - 2;      // odd count: the last instruction fetches tables NT-2 (again) and NT-1 --
-        const char *b = ubase + (size_t)i * cstride_bytes;      // no divergent branch, no spare table, no extra LDS
-        __builtin_amdgcn_global_load_lds((lc_gptr *)(b + voff), (lc_lptr *)(stg + i * 64), 16, 0, 0);
+        // no divergent branch, no spare table, no extra LDS
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(w, (lc_lptr *)(stg + i * 64), 16, voff, soff + (u32)i * cstride_bytes, 0, 0);
     }
 }
 
@@ -274,26 +277,29 @@ __device__ __forceinline__ void rows_body(const u64 *__restrict__ in, double *__
     const int tid = threadIdx.x;
     const size_t poly_words = (size_t)k * N, ct_words = 2 * poly_words;
     const size_t base = ((size_t)wk.blk * 64 + 8 * wk.line) * ct_words + (size_t)wk.poly * poly_words + (size_t)wk.prime * N;
+    // this workgroup's window of each tensor (gwin, fp64_core.h): eight ciphertexts from `base`; byte offsets inside it
+    // are  vo + uniform  and stay below 2^31 (checked by fhe_dct_f64_launch)
+    const gwin_t win_in = gwin(in + base), win_mid = gwin(mid + base);
+    const u32 vo = (u32)tid * 8u, ctb = (u32)(ct_words * 8);
     double w0[E - 1];
     load_tw<L, LE, 0>(w0, tw, tid);
     double x[4][E];
-    // d_m +- d_(7-m) in integers (inputs are < 2^47), then one exact move to double.  Two line
-    // pairs are kept in flight; the compiler fences stop it from hoisting every load to the top.
-    constexpr u64 OFF = 1ULL << 48;
+    // d_m + d_(7-m) in integers (inputs are < 2^47), then one exact move to double; d_m - d_(7-m) as the difference
+    // of the two biased doubles.  Two line pairs are kept in flight; the compiler fences stop it from hoisting every
+    // load to the top.
     u64 ra[2][E], rb[2][E];
     auto issue = [&](int m) {
-        const u64 *a = in + base + (size_t)m * ct_words + tid, *b = in + base + (size_t)(7 - m) * ct_words + tid;
 #pragma unroll
         for (int r = 0; r < E; r++) {       // pass-0 mapping: coefficient r*TP + tid
-            ra[m & 1][r] = a[r * TP];
-            rb[m & 1][r] = b[r * TP];
+            ra[m & 1][r] = gld_u64(win_in, vo, (u32)m * ctb + r * TP * 8);
+            rb[m & 1][r] = gld_u64(win_in, vo, (u32)(7 - m) * ctb + r * TP * 8);
         }
     };
     auto combine = [&](int m) {
 #pragma unroll
         for (int r = 0; r < E; r++) {
             const u64 A = ra[m & 1][r], B = rb[m & 1][r];
-            x[m][r] = HALF ? u52_to_f64(A + OFF - B) - (double)OFF : u52_to_f64(A + B);
+            x[m][r] = HALF ? u52_biased(A) - u52_biased(B) : u52_to_f64(A + B);
         }
     };
     if constexpr (LE >= 4) {
@@ -316,31 +322,33 @@ __device__ __forceinline__ void rows_body(const u64 *__restrict__ in, double *__
             asm volatile("" ::: "memory");
         }
     }
-    const double *cp = consts + (size_t)FIRST * k * N + (size_t)wk.prime * N + tid;
     const size_t cstride = (size_t)k * N;
+    const gwin_t win_c = gwin(consts + (size_t)FIRST * cstride + (size_t)wk.prime * N);
+    const u32 csb = (u32)(cstride * 8);
     double cn[9];
     auto fetch = [&](int r) {
 #pragma unroll
-        for (int i = 0; i < NC; i++) cn[i] = cp[(size_t)i * cstride + r * TP];
+        for (int i = 0; i < NC; i++) cn[i] = gld_f64(win_c, vo, (u32)i * csb + r * TP * 8);
     };
     int phase = 0;
     ntt_fwd<L, LE, 4>(x, w0, tw, p, pinv, lds, tid, phase, [&] { if (LE >= 4) fetch(0); });
     // LDSC: two staging buffers of NC x 64 doubles per wave (9 x 512 B x 2 x 8 waves = the two exchange buffers exactly)
     const int lane = tid & 63;
     double *stg = lds + (tid >> 6) * (2 * NC * 64);
-    const char *sbase = (const char *)(consts + (size_t)FIRST * cstride + (size_t)wk.prime * N);
     const u32 svoff = (u32)(((size_t)(lane >> 5) * cstride + (tid & ~63) + 2 * (lane & 31)) * sizeof(double));
     constexpr int NDMA = (NC + 1) / 2;      // instructions per slot
     if constexpr (LDSC) {
+        // keep the slots' arithmetic below the barrier: hoisted into the last transform pass it costs registers there
+        __builtin_amdgcn_sched_barrier(0);
         __syncthreads();                    // every wave is done with the exchange buffers
-        stage_consts<NC>(sbase, svoff, cstride * sizeof(double), stg, lane);
+        stage_consts<NC>(win_c, svoff, 0, csb, stg);
     }
 #pragma unroll
     for (int r = 0; r < E; r++) {
         double c[9];
         if constexpr (LDSC) {
             // slot r+1 on its way into the other buffer (last read in slot r-1) while slot r is evaluated
-            if (r + 1 < E) stage_consts<NC>(sbase + (size_t)(r + 1) * TP * sizeof(double), svoff, cstride * sizeof(double), stg + ((r + 1) & 1) * NC * 64, lane);
+            if (r + 1 < E) stage_consts<NC>(win_c, svoff, (r + 1) * TP * 8, csb, stg + ((r + 1) & 1) * NC * 64);
             if (r + 1 < E) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             const double *sr = stg + (r & 1) * NC * 64 + lane;
@@ -366,12 +374,12 @@ __device__ __forceinline__ void rows_body(const u64 *__restrict__ in, double *__
     }
 #pragma unroll
     for (int m = 0; m < 4; m++) {
-        double *o = mid + base + (size_t)(2 * m + HALF) * ct_words + tid;
+        const u32 so = (u32)(2 * m + HALF) * ctb;
         if constexpr (PACK) {
-            store_packed<E, TP>((u64 *)o, x[m]);
+            store_packed<E, TP>((char *)(mid + base), vo, so, x[m]);
         } else {
 #pragma unroll
-            for (int r = 0; r < E; r++) o[r * TP] = x[m][r];
+            for (int r = 0; r < E; r++) gst_f64(win_mid, vo, so + r * TP * 8, x[m][r]);
         }
     }
 }
@@ -403,17 +411,21 @@ __device__ __forceinline__ void cols_body(const double *__restrict__ mid, u64 *_
     const int tid = threadIdx.x;
     const size_t poly_words = (size_t)k * N, ct_words = 2 * poly_words;
     const size_t base = ((size_t)wk.blk * 64 + wk.line) * ct_words + (size_t)wk.poly * poly_words + (size_t)wk.prime * N;
-    const size_t row_stride = 8 * ct_words;
     const size_t cstride = (size_t)k * N;
-    const double *cp = consts + (size_t)FIRST * cstride + (size_t)wk.prime * N + tid;
+    // windows as in rows_body: a column spans 57 ciphertexts from `base` (rows 8 ciphertexts apart), the constants
+    // of this prime 76 tables; all offsets below 2^31 (fhe_dct_f64_launch)
+    const gwin_t win_mid = gwin(mid + base), win_out = gwin(out + base);
+    const gwin_t win_c = gwin(consts + (size_t)FIRST * cstride + (size_t)wk.prime * N);
     // per-output scale: row 2m+HALF, column wk.line -> constant 12 + 8*row + col
-    const double *sp = consts + (size_t)(12 + 8 * HALF + wk.line) * cstride + (size_t)wk.prime * N + tid;
+    const gwin_t win_s = gwin(consts + (size_t)(12 + 8 * HALF + wk.line) * cstride + (size_t)wk.prime * N);
+    const u32 vo = (u32)tid * 8u, rsb = (u32)(ct_words * 64), csb = (u32)(cstride * 8);     // bytes per row / per table
+    const double pbias = p + 4503599627370496.0;
     double cn[9], sn[4];
     auto fetch = [&](int r) {
 #pragma unroll
-        for (int i = 0; i < NC; i++) cn[i] = cp[(size_t)i * cstride + r * TP];
+        for (int i = 0; i < NC; i++) cn[i] = gld_f64(win_c, vo, (u32)i * csb + r * TP * 8);
 #pragma unroll
-        for (int m = 0; m < 4; m++) sn[m] = sp[(size_t)(16 * m) * cstride + r * TP];
+        for (int m = 0; m < 4; m++) sn[m] = gld_f64(win_s, vo, (u32)(16 * m) * csb + r * TP * 8);
     };
     double wl[E - 1];
     if constexpr (!PACK) {           // in flight behind the bulk loads
@@ -428,9 +440,11 @@ __device__ __forceinline__ void cols_body(const double *__restrict__ mid, u64 *_
         u64 wa[4][5], wb[4][5];
 #pragma unroll
         for (int m = 0; m < 4; m++) {
-            const u64 *a = (const u64 *)(mid + base + (size_t)m * row_stride) + tid, *b = (const u64 *)(mid + base + (size_t)(7 - m) * row_stride) + tid;
 #pragma unroll
-            for (int q = 0; q < 5; q++) { wa[m][q] = a[q * TP]; wb[m][q] = b[q * TP]; }
+            for (int q = 0; q < 5; q++) {
+                wa[m][q] = gld_u64(win_mid, vo, (u32)m * rsb + q * TP * 8);
+                wb[m][q] = gld_u64(win_mid, vo, (u32)(7 - m) * rsb + q * TP * 8);
+            }
         }
 #pragma unroll
         for (int m = 0; m < 4; m++) {
@@ -447,10 +461,9 @@ __device__ __forceinline__ void cols_body(const double *__restrict__ mid, u64 *_
     } else {
 #pragma unroll
         for (int m = 0; m < 4; m++) {
-            const double *a = mid + base + (size_t)m * row_stride + tid, *b = mid + base + (size_t)(7 - m) * row_stride + tid;
 #pragma unroll
             for (int r = 0; r < E; r++) {
-                const double A = a[r * TP], B = b[r * TP];
+                const double A = gld_f64(win_mid, vo, (u32)m * rsb + r * TP * 8), B = gld_f64(win_mid, vo, (u32)(7 - m) * rsb + r * TP * 8);
                 x[m][r] = HALF ? A - B : A + B;
             }
         }
@@ -475,13 +488,8 @@ __device__ __forceinline__ void cols_body(const double *__restrict__ mid, u64 *_
     ntt_inv<L, LE, 4, BIG>(x, wl, itw, p, pinv, lds, tid, phase);
 #pragma unroll
     for (int m = 0; m < 4; m++) {
-        u64 *o = out + base + (size_t)(2 * m + HALF) * row_stride + tid;
 #pragma unroll
-        for (int r = 0; r < E; r++) {
-            double v = x[m][r];
-            v = v < 0.0 ? v + p : v;
-            o[r * TP] = f64_to_u52(v);
-        }
+        for (int r = 0; r < E; r++) gst_u64(win_out, vo, (u32)(2 * m + HALF) * rsb + r * TP * 8, f64_to_residue(x[m][r], pbias));
     }
 }
 
@@ -779,6 +787,10 @@ int fhe_dct_f64_launch(const fhe_ctx *c, const fhe_dct_plan *plan, const u64 *in
     const u64 items = n_blocks * 8 * 2 * c->k;   // (block, line, poly, prime), multiple of 8
     const u64 grid = items * 2;
     if (grid > 0x7fffffffULL) return fail(FHE_ERR_PARAM, "too many blocks for one launch");
+    // the kernels address each tensor through 32-bit byte offsets inside a per-workgroup window (gwin): at most one
+    // block of 64 ciphertexts (2 k n words each) or the 76 constant tables (k n doubles each) -- both below 2^31 bytes
+    // for k n < 2^21, far beyond any context this path accepts (n <= 8192)
+    if ((u64)c->k * c->n >= (1ULL << 21)) return fail(FHE_ERR_PARAM, "fused FP64 path: a block of ciphertexts exceeds the 2 GiB addressing window");
     const bool big = c->max_prime_bits > 40;
     if (c->opt.dct_one_launch && which == 3 && c->logn == 12 && dct_shape_le(c) == 3 && c->max_prime_bits <= 37 && c->opt.dct_pack && c->d_arrived) {
         const u64 n_units = n_blocks * 2 * c->k;

@@ -38,6 +38,31 @@ __device__ __forceinline__ void mmv(double (&y)[K], const double (&w)[K], double
 // exact integer <-> double moves: for 0 <= v < 2^52, bits(2^52 + v) = 0x4330000000000000 | v
 __device__ __forceinline__ double u52_to_f64(u64 v) { return __longlong_as_double((long long)(v | 0x4330000000000000ULL)) - 4503599627370496.0; }
 __device__ __forceinline__ u64 f64_to_u52(double v) { return (u64)__double_as_longlong(v + 4503599627370496.0) & 0x000FFFFFFFFFFFFFULL; }
+// the biased double 2^52 + v itself: (2^52 + a) - (2^52 + b) = a - b exactly for a, b < 2^52, one FP64 operation for the
+// difference of two integers instead of a 64-bit integer subtract and two FP64 subtracts
+__device__ __forceinline__ double u52_biased(u64 v) { return __longlong_as_double((long long)(v | 0x4330000000000000ULL)); }
+// centred residue -p < v < p -> canonical [0, p): v + 2^52 or v + (2^52 + p), both exact (0 <= v + p < 2^52), so the
+// sign only selects the addend (pbias = 2^52 + p) and the low 52 bits of the one sum are the residue
+__device__ __forceinline__ u64 f64_to_residue(double v, double pbias) {
+    return (u64)__double_as_longlong(v + (v < 0.0 ? pbias : 4503599627370496.0)) & 0x000FFFFFFFFFFFFFULL;
+}
+
+// Global memory through a buffer resource.  The fused kernels address a window of one tensor per workgroup: a base that
+// depends only on blockIdx (uniform: the full 64-bit address is put into the descriptor with scalar instructions) plus
+// offsets of the form  thread * 8 + uniform.  `buffer_load/store_dwordx2 v, voff, s[rsrc], soff offen` takes exactly
+// that -- one 32-bit VGPR offset shared by every access of the thread and one SGPR per uniform part -- where a flat
+// pointer costs a 64-bit VGPR pair and VALU adds per access (the register stride of 4096 B does not fit an immediate).
+// Raw buffer (stride 0); num_records is the maximum, so the hardware range check never fires and never replaces an
+// access with zeros: the host checks instead that every window is below 2^31 bytes (fhe_dct_f64_launch).
+typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+typedef __amdgpu_buffer_rsrc_t gwin_t;
+__device__ __forceinline__ gwin_t gwin(const void *base) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, -1, 0x00020000 /* DATA_FORMAT = 32 */);
+}
+__device__ __forceinline__ u64 gld_u64(gwin_t w, u32 voff, u32 soff) { return __builtin_bit_cast(u64, __builtin_amdgcn_raw_buffer_load_b64(w, voff, soff, 0)); }
+__device__ __forceinline__ double gld_f64(gwin_t w, u32 voff, u32 soff) { return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(w, voff, soff, 0)); }
+__device__ __forceinline__ void gst_u64(gwin_t w, u32 voff, u32 soff, u64 v) { __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), w, voff, soff, 0); }
+__device__ __forceinline__ void gst_f64(gwin_t w, u32 voff, u32 soff, double v) { __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), w, voff, soff, 0); }
 
 // Even / odd half of one LL&M line (homo/fhe_image.h:215-242) on a single NTT slot.
 // In:  even: x[m] = d_m + d_(7-m) (tmp0..tmp3);  odd: x[m] = d_m - d_(7-m) (tmp7,tmp6,tmp5,tmp4).
