@@ -103,6 +103,14 @@ SIGNATURES = {
     "fhe_filter2d_scratch_bytes": (_sz, [_vp, _vp, _u32, _u64, _u64, _i]),
     "fhe_filter2d": (_i, [_vp, _vp, _vp, _u64, _u32, _i, _vp, _vp, _u64, _vp, _sz, _vp]),
     "fhe_filter_path": (_i, [_vp]),
+    "fhe_weight_table_create": (_i, [_vp, _vp, _u32, _i, _i, _vp, C.POINTER(_vp)]),
+    "fhe_weight_table_destroy": (_i, [_vp]),
+    "fhe_weight_table_count": (_i, [_vp]),
+    "fhe_weight_table_distinct": (_i, [_vp]),
+    "fhe_remap_scratch_bytes": (_sz, [_vp, _vp, _u32, _u64, _u64, _i]),
+    "fhe_remap": (_i, [_vp, _vp, _vp, _u64, _u32, _i, _vp, _vp, _u32, _vp, _i, _u64, _vp, _sz, _vp]),
+    "fhe_remap_path": (_i, [_vp]),
+    "fhe_resample_axis_plan": (_i, [_u32, _u32, _i, _i, _i, _i, C.POINTER(_u32), _vp, _vp]),
     "fhe_fill_random": (_i, [_vp, _vp, _u64, _u64, _u64, _vp]),
     "fhe_digest": (_i, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "fhe_count_unreduced": (_i, [_vp, _vp, _u64, _vp, _vp]),
@@ -157,7 +165,7 @@ SIGNATURES = {
     "fhe_io_transfer": (_i, [_vp, _u64, _u64, _u32, _u32, _u32, _vp, _u32]),
 }
 # entry points whose int return value is a count (>= 0) or an error (< 0)
-_COUNT_RETURN = {"fhe_default_coeff_modulus", "fhe_frac_encode", "fhe_dct_path", "fhe_arith_path", "fhe_filter_path", "fhe_filter_plan_taps", "fhe_ctx_device", "fhe_ctx_has_ctct_tables"}
+_COUNT_RETURN = {"fhe_default_coeff_modulus", "fhe_frac_encode", "fhe_dct_path", "fhe_arith_path", "fhe_filter_path", "fhe_filter_plan_taps", "fhe_remap_path", "fhe_weight_table_count", "fhe_weight_table_distinct", "fhe_ctx_device", "fhe_ctx_has_ctct_tables"}
 
 
 def load():

@@ -768,12 +768,12 @@ void resize_index(u32 src_w, u32 src_h, u32 dst_w, u32 dst_h, ResizeIndex &ix) {
     ix.colx.resize((size_t)dst_w * 4);
     ix.rows_of.resize((size_t)dst_h * 4);
     for (u32 x = 0; x < dst_w; ++x) {
-        const float u = (float)((float)x / (float)(dst_w - 1) * (float)src_w - 0.5);      // homo/fhe_resize.h:382
+        const float u = fhe_resize_ref_coord(x, dst_w, src_w);             // homo/fhe_resize.h:382
         const int xi = (int)u;
         for (int i = 0; i < 4; ++i) ix.colx[x * 4 + i] = (u32)clampi(xi - 1 + i, 0, (int)src_w - 1);
     }
     for (u32 y = 0; y < dst_h; ++y) {
-        const float v = (float)((float)y / (float)(dst_h - 1) * (float)src_h - 0.5);      // :351
+        const float v = fhe_resize_ref_coord(y, dst_h, src_h);                 // :351
         const int yi = (int)v;
         for (int j = 0; j < 4; ++j) ix.rows_of[y * 4 + j] = (u32)clampi(yi - 1 + j, 0, (int)src_h - 1);
     }
@@ -1245,10 +1245,10 @@ extern "C" int fhe_resize_sample_plan(uint32_t src_w, uint32_t src_h, uint32_t d
     if ((u64)src_w * src_h > 0xffffffffULL) return fail(FHE_ERR_PARAM, "source image too large");
     const u32 nt = bicubic ? 16 : 4;
     for (u32 y = 0; y < dst_h; ++y) {
-        const float v = (float)((float)y / (float)(dst_h - 1) * (float)src_h - 0.5);          // homo/fhe_resize.h:351
+        const float v = fhe_resize_ref_coord(y, dst_h, src_h);                     // homo/fhe_resize.h:351
         const int yi = (int)v;                                                                // :264 / :229
         for (u32 x = 0; x < dst_w; ++x) {
-            const float u = (float)((float)x / (float)(dst_w - 1) * (float)src_w - 0.5);      // :382
+            const float u = fhe_resize_ref_coord(x, dst_w, src_w);             // :382
             const int xi = (int)u;
             const size_t o = (size_t)y * dst_w + x;
             if (xfract) xfract[o] = (double)(u - floorf(u));                                  // :262
@@ -1344,7 +1344,7 @@ extern "C" int fhe_resize_source_rows(uint32_t src_h, uint32_t dst_h, uint32_t r
     if (!src_h || dst_h < 2 || row0 >= row1 || row1 > dst_h || !first || !count) return fail(FHE_ERR_PARAM, "bad row range");
     u32 lo = 0xffffffffu, hi = 0;
     for (u32 y = row0; y < row1; ++y) {
-        const float v = (float)((float)y / (float)(dst_h - 1) * (float)src_h - 0.5);          // homo/fhe_resize.h:351
+        const float v = fhe_resize_ref_coord(y, dst_h, src_h);                     // homo/fhe_resize.h:351
         const int yi = (int)v;
         const u32 a = (u32)clampi(bicubic ? yi - 1 : yi, 0, (int)src_h - 1), z = (u32)clampi(bicubic ? yi + 2 : yi + 1, 0, (int)src_h - 1);
         if (a < lo) lo = a;

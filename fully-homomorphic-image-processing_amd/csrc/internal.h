@@ -124,6 +124,10 @@ struct fhe_dct_plan {
     bool has_quant = false;
 };
 
+// destination index -> source coordinate as the reference's ResizeImage computes it (homo/fhe_resize.h:351,382: float arithmetic, the
+// half-pixel shift in double before the store): shared by fhe_resize_sample_plan / fhe_resize_source_rows and fhe_resample_axis_plan
+inline float fhe_resize_ref_coord(u32 i, u32 dst_len, u32 src_len) { return (float)((float)i / (float)(dst_len - 1) * (float)src_len - 0.5); }
+
 #define DISPATCH_L(logn, ...)                                                    \
     switch (logn) {                                                              \
         case 10: { constexpr int L = 10; __VA_ARGS__; } break;                   \

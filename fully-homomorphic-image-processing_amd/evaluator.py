@@ -282,6 +282,42 @@ class FilterPlan:
             self.h = None
 
 
+REMAP_MAX_TAPS = 64        # FHE_REMAP_MAX_TAPS in include/fhe_hip.h
+REMAP_MAX_WEIGHTS = 4096   # FHE_REMAP_MAX_WEIGHTS
+REMAP_SKIP = 0xFFFFFFFF    # FHE_REMAP_SKIP: an unused slot of Evaluator.remap's weight ids
+
+
+class WeightTable:
+    """The plaintext weights Evaluator.remap indexes (fhe_weight_table_create): a 1-D array of public values, each distinct one encoded
+    (FractionalEncoder(int_coeffs, frac_coeffs)), lifted and transformed once and kept on the device.  Entries that encode to the
+    zero plaintext are remembered as such: their slots are skipped."""
+
+    def __init__(self, ctx, values, int_coeffs=100, frac_coeffs=100):
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if v.ndim != 1 or v.size == 0:
+            raise ValueError("WeightTable: values must be a non-empty 1-D array, got shape %r" % (v.shape,))
+        if not np.all(np.isfinite(v)):
+            raise ValueError("WeightTable: values must be finite")
+        if np.unique(v[v != 0.0]).size > REMAP_MAX_WEIGHTS:
+            raise ValueError("WeightTable: %d distinct values, at most FHE_REMAP_MAX_WEIGHTS = %d (round them: weight_bits)"
+                             % (np.unique(v[v != 0.0]).size, REMAP_MAX_WEIGHTS))
+        self.ctx, self.values = ctx, v
+        h = C.c_void_p()
+        _lib.call("fhe_weight_table_create", ctx.h, v.ctypes.data_as(C.c_void_p), int(v.size), int_coeffs, frac_coeffs, _stream(), C.byref(h))
+        self.h = h
+        self.count = int(_lib.call("fhe_weight_table_count", h))
+        self.distinct = int(_lib.call("fhe_weight_table_distinct", h))       # distinct entries that do not encode to zero
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h:
+            try:
+                _lib.load().fhe_weight_table_destroy(h)
+            except Exception:
+                pass
+            self.h = None
+
+
 def check_evaluation_keys(ctx, evk_ntt, dbc, need, who):
     """The library takes the keys as a bare pointer and reads need * fhe_evk_words(ctx, dbc) words behind it (include/fhe_hip.h): the host
     checks that the tensor it hands over holds them -- a key tensor made for another decomposition bit count (fewer digits), another context or
@@ -602,3 +638,61 @@ class Evaluator:
         _lib.call("fhe_filter2d", self.ctx.h, plan.h, _ptr(src), n_src, size, int(bool(src_is_ntt)), t.ctypes.data_as(C.c_void_p), _ptr(out), count,
                   _ptr(scr), nbytes, _stream())
         return out
+
+    def remap(self, table, src, taps, wids, out=None, src_is_ntt=False, out_is_ntt=False):
+        """Resampling with public per-output weights (fhe_remap, include/fhe_hip.h): output c = the sum over the slots p with
+        wids[c][p] != REMAP_SKIP (and a weight that does not encode to zero) of multiply_plain(src[taps[c][p]], encode(table.values[wids[c][p]])),
+        bit for bit the op-by-op composition.  src: [n_src, size, k, n] (never written); taps, wids: integer arrays [count][T]; returns
+        [count, size, k, n].  src_is_ntt: src already is ntt_forward of the ciphertexts; out_is_ntt: the result is left as ntt_forward of
+        the specified output (a second remap takes it with src_is_ntt)."""
+        kn = (self.ctx.k, self.ctx.n)
+        if not (isinstance(src, torch.Tensor) and src.dim() >= 4 and tuple(src.shape[-2:]) == kn and src.dtype == torch.int64 and src.is_contiguous()
+                and src.device == self.ctx.device and src.shape[-3] >= 1):
+            raise ValueError("remap: `src` must be a contiguous int64 tensor [..., size, k, n] = [..., size, %d, %d] on the context's device, got %r"
+                             % (kn + (tuple(getattr(src, "shape", ())),)))
+        if table.ctx is not self.ctx:
+            raise ValueError("remap: the weight table was built for another context")
+        size = int(src.shape[-3])
+        n_src = src.numel() // (size * kn[0] * kn[1])
+        t, w = np.asarray(taps), np.asarray(wids)
+        if t.ndim != 2 or w.shape != t.shape or t.dtype.kind not in "iu" or w.dtype.kind not in "iu" or not 1 <= t.shape[1] <= REMAP_MAX_TAPS:
+            raise ValueError("remap: `taps` and `wids` must be integer arrays of one shape [count][T], 1 <= T <= %d, got %r %s and %r %s"
+                             % (REMAP_MAX_TAPS, t.shape, t.dtype, w.shape, w.dtype))
+        live = w != REMAP_SKIP
+        if w.size and (int(w.min()) < 0 or (np.any(live) and int(w[live].max()) >= table.count)):
+            raise ValueError("remap: weight ids must index the %d entries of the table (or be REMAP_SKIP)" % table.count)
+        if np.any(live) and (int(t[live].min()) < 0 or int(t[live].max()) >= n_src):
+            raise ValueError("remap: taps must index the %d source ciphertexts, got values in [%d, %d]" % (n_src, int(t[live].min()), int(t[live].max())))
+        if t.shape[0] and not np.all(np.any(live, axis=1)):
+            raise ValueError("remap: output %d has no live slot" % int(np.flatnonzero(~np.any(live, axis=1))[0]))
+        t = np.ascontiguousarray(np.where(live, t, 0), dtype=np.uint32)
+        w = np.ascontiguousarray(w, dtype=np.uint32)
+        count, width = int(t.shape[0]), int(t.shape[1])
+        shape = (count, size) + kn
+        if out is not None:
+            if not (isinstance(out, torch.Tensor) and tuple(out.shape) == shape and out.dtype == torch.int64 and out.is_contiguous() and out.device == src.device):
+                raise ValueError("remap: `out` must be a contiguous int64 tensor %r on the device of `src`, got %r" % (shape, tuple(getattr(out, "shape", ()))))
+            a0, a1 = src.data_ptr(), src.data_ptr() + src.numel() * 8
+            b0, b1 = out.data_ptr(), out.data_ptr() + out.numel() * 8
+            if out.numel() and a0 < b1 and b0 < a1:
+                raise ValueError("remap: `out` overlaps `src`")
+        else:
+            out = torch.empty(shape, dtype=torch.int64, device=src.device)
+        if count == 0:
+            return out
+        nbytes = _lib.load().fhe_remap_scratch_bytes(self.ctx.h, table.h, size, n_src, count, int(bool(src_is_ntt)))
+        scr = self._scratch_buf(nbytes)
+        _lib.call("fhe_remap", self.ctx.h, table.h, _ptr(src), n_src, size, int(bool(src_is_ntt)), t.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p),
+                  width, _ptr(out), int(bool(out_is_ntt)), count, _ptr(scr), nbytes, _stream())
+        return out
+
+    def resize_plain(self, plan, src, tables=None, out=None, src_is_ntt=False, int_coeffs=100, frac_coeffs=100):
+        """A separable resize with public weights: the two remap passes of `plan` (circuits.resize_plan) with the intermediate kept in NTT
+        form, so every ciphertext is transformed forward once and back once.  src: the records of the source rows plan["source_rows"]
+        names, [rows * src_w * channels, size, k, n]; returns the records of the plan's destination rows.  tables: the passes' WeightTables
+        (built from the plan when None; a server that runs many bands builds them once)."""
+        if tables is None:
+            tables = [WeightTable(self.ctx, p["values"], int_coeffs, frac_coeffs) for p in plan["passes"]]
+        first, second = plan["passes"]
+        mid = self.remap(tables[0], src.view(-1, *src.shape[-3:]), first["taps"], first["wids"], src_is_ntt=src_is_ntt, out_is_ntt=True)
+        return self.remap(tables[1], mid, second["taps"], second["wids"], out=out, src_is_ntt=True)

@@ -1656,6 +1656,121 @@ inline std::vector<Ciphertext> filter2d(const SEALContext &ctx, const std::vecto
     detail::check(fhe_stream_sync(nullptr), "sync");
     return res;
 }
+// Resampling with public per-output weights (fhe_remap, include/fhe_hip.h): out[c] = sum over the slots p with wids[c * T + p] != FHE_REMAP_SKIP
+// (and a weight that does not encode to zero) of multiply_plain(src[taps[c * T + p]], encode(weights[wids[c * T + p]])) -- bit for bit the
+// Evaluator calls, with one transform per source and one per output.  taps, wids: [count][T].  All sources have one size.
+inline std::vector<Ciphertext> remap(const SEALContext &ctx, const std::vector<Ciphertext> &src, const std::vector<double> &weights,
+                                     const std::vector<uint32_t> &taps, const std::vector<uint32_t> &wids, uint32_t T, int int_coeffs = 100,
+                                     int frac_coeffs = 100) {
+    const detail::CtxState &s = *ctx.state();
+    if (src.empty()) throw std::invalid_argument("remap needs source ciphertexts");
+    if (weights.empty()) throw std::invalid_argument("remap needs a weight table");
+    if (!T || taps.size() % T || wids.size() != taps.size()) throw std::invalid_argument("remap needs T taps and T weight ids per output");
+    const size_t count = taps.size() / T;
+    const int size = src[0].size();
+    const size_t ctw = (size_t)size * s.poly_words();
+    detail::DevBuf in(src.size() * ctw), out((count ? count : 1) * ctw);
+    for (size_t i = 0; i < src.size(); ++i) {
+        if (src[i].size() != size) throw std::invalid_argument("remap needs sources of one size");
+        detail::check(fhe_copy(in.ptr() + i * ctw, src[i].ptr(), ctw * 8, nullptr), "copy");
+    }
+    fhe_weight_table *table = nullptr;
+    detail::check(fhe_weight_table_create(s.h, weights.data(), (uint32_t)weights.size(), int_coeffs, frac_coeffs, nullptr, &table), "weight table");
+    const size_t bytes = fhe_remap_scratch_bytes(s.h, table, (uint32_t)size, src.size(), count, 0);
+    detail::DevBuf scratch((bytes + 7) / 8 + 1);
+    int rc = fhe_remap(s.h, table, in.ptr(), src.size(), (uint32_t)size, 0, taps.data(), wids.data(), T, out.ptr(), 0, count, scratch.ptr(), bytes, nullptr);
+    fhe_weight_table_destroy(table);
+    detail::check(rc, "remap");
+    std::vector<Ciphertext> res(count);
+    for (size_t i = 0; i < count; ++i) {
+        res[i] = src[0];                                      // the shape; ptr() below detaches the handle (copy on write)
+        detail::check(fhe_copy(res[i].ptr(), out.ptr() + i * ctw, ctw * 8, nullptr), "copy");
+    }
+    detail::check(fhe_stream_sync(nullptr), "sync");
+    return res;
+}
+// A separable resize with public weights: src holds src_w * src_h * channels records (pixel (x, y), channel c at (y * src_w + x) * channels + c),
+// the result dst_w * dst_h * channels records in the same order.  Two fhe_remap passes over the axis plans of fhe_resample_axis_plan
+// (kernel: FHE_RESAMPLE_*, convention: FHE_RESAMPLE_HALF_PIXEL / _REFERENCE), the intermediate kept in NTT form; the axis that leaves
+// the smaller intermediate runs first (the passes commute as ring maps: the bits do not depend on the order).
+inline std::vector<Ciphertext> resize_plain(const SEALContext &ctx, const std::vector<Ciphertext> &src, uint32_t src_w, uint32_t src_h, uint32_t dst_w,
+                                            uint32_t dst_h, int kernel = FHE_RESAMPLE_CATMULL_ROM, uint32_t channels = 1, bool antialias = false,
+                                            int convention = FHE_RESAMPLE_HALF_PIXEL, int weight_bits = 0, int int_coeffs = 100, int frac_coeffs = 100) {
+    const detail::CtxState &s = *ctx.state();
+    if (!channels || src.size() != (size_t)src_w * src_h * channels) throw std::invalid_argument("resize_plain needs src_w * src_h * channels ciphertexts");
+    // record indices travel as uint32 (fhe_remap's taps): every source, intermediate and result record must have one
+    const uint64_t widest = (uint64_t)(src_w > dst_w ? src_w : dst_w) * (src_h > dst_h ? src_h : dst_h);
+    if (widest > 0xffffffffULL / channels) throw std::invalid_argument("resize_plain: image too large (record indices are 32 bits)");
+    struct Axis { uint32_t T; std::vector<uint32_t> taps, wids; std::vector<double> w, values; };
+    auto axis = [&](uint32_t from, uint32_t to) {
+        Axis a;
+        a.T = 0;
+        detail::check(fhe_resample_axis_plan(from, to, kernel, antialias ? 1 : 0, convention, weight_bits, &a.T, nullptr, nullptr), "resample_axis_plan");
+        a.taps.resize((size_t)to * a.T);
+        a.w.resize((size_t)to * a.T);
+        detail::check(fhe_resample_axis_plan(from, to, kernel, antialias ? 1 : 0, convention, weight_bits, &a.T, a.taps.data(), a.w.data()), "resample_axis_plan");
+        a.wids.resize(a.w.size());
+        for (size_t i = 0; i < a.w.size(); ++i) {
+            size_t d = 0;
+            while (d < a.values.size() && a.values[d] != a.w[i]) ++d;
+            if (d == a.values.size()) a.values.push_back(a.w[i]);
+            a.wids[i] = (uint32_t)d;
+        }
+        return a;
+    };
+    const Axis ax = axis(src_w, dst_w), ay = axis(src_h, dst_h);
+    const bool h_first = (uint64_t)src_h * dst_w < (uint64_t)dst_h * src_w;       // equal: vertical first, as circuits.resize_plan
+    const uint32_t mid_w = h_first ? dst_w : src_w, mid_h = h_first ? src_h : dst_h;
+    // pass over x: [lines][from_w][channels] -> [lines][to_w][channels]; pass over y: [from_h][width][channels] -> [to_h][width][channels]
+    auto plan_x = [&](uint32_t lines, uint32_t from_w, std::vector<uint32_t> &taps, std::vector<uint32_t> &wids) {
+        for (uint32_t y = 0; y < lines; ++y)
+            for (uint32_t x = 0; x < dst_w; ++x)
+                for (uint32_t c = 0; c < channels; ++c)
+                    for (uint32_t p = 0; p < ax.T; ++p) {
+                        taps.push_back((uint32_t)(((uint64_t)y * from_w + ax.taps[(size_t)x * ax.T + p]) * channels + c));
+                        wids.push_back(ax.wids[(size_t)x * ax.T + p]);
+                    }
+    };
+    auto plan_y = [&](uint32_t width, std::vector<uint32_t> &taps, std::vector<uint32_t> &wids) {
+        for (uint32_t y = 0; y < dst_h; ++y)
+            for (uint32_t x = 0; x < width; ++x)
+                for (uint32_t c = 0; c < channels; ++c)
+                    for (uint32_t p = 0; p < ay.T; ++p) {
+                        taps.push_back((uint32_t)(((uint64_t)ay.taps[(size_t)y * ay.T + p] * width + x) * channels + c));
+                        wids.push_back(ay.wids[(size_t)y * ay.T + p]);
+                    }
+    };
+    std::vector<uint32_t> t1, w1, t2, w2;
+    if (h_first) { plan_x(src_h, src_w, t1, w1); plan_y(dst_w, t2, w2); }
+    else { plan_y(src_w, t1, w1); plan_x(dst_h, src_w, t2, w2); }
+    const Axis &a1 = h_first ? ax : ay, &a2 = h_first ? ay : ax;
+    const int size = src[0].size();
+    const size_t ctw = (size_t)size * s.poly_words();
+    const size_t n_mid = (size_t)mid_w * mid_h * channels, count = (size_t)dst_w * dst_h * channels;
+    detail::DevBuf in(src.size() * ctw), mid(n_mid * ctw), out(count * ctw);
+    for (size_t i = 0; i < src.size(); ++i) {
+        if (src[i].size() != size) throw std::invalid_argument("resize_plain needs sources of one size");
+        detail::check(fhe_copy(in.ptr() + i * ctw, src[i].ptr(), ctw * 8, nullptr), "copy");
+    }
+    fhe_weight_table *tab1 = nullptr, *tab2 = nullptr;
+    detail::check(fhe_weight_table_create(s.h, a1.values.data(), (uint32_t)a1.values.size(), int_coeffs, frac_coeffs, nullptr, &tab1), "weight table");
+    int rc = fhe_weight_table_create(s.h, a2.values.data(), (uint32_t)a2.values.size(), int_coeffs, frac_coeffs, nullptr, &tab2);
+    if (rc) { fhe_weight_table_destroy(tab1); detail::check(rc, "weight table"); }
+    const size_t bytes = fhe_remap_scratch_bytes(s.h, tab1, (uint32_t)size, src.size(), n_mid, 0);
+    detail::DevBuf scratch((bytes + 7) / 8 + 1);
+    rc = fhe_remap(s.h, tab1, in.ptr(), src.size(), (uint32_t)size, 0, t1.data(), w1.data(), a1.T, mid.ptr(), 1, n_mid, scratch.ptr(), bytes, nullptr);
+    if (!rc) rc = fhe_remap(s.h, tab2, mid.ptr(), n_mid, (uint32_t)size, 1, t2.data(), w2.data(), a2.T, out.ptr(), 0, count, nullptr, 0, nullptr);
+    fhe_weight_table_destroy(tab1);
+    fhe_weight_table_destroy(tab2);
+    detail::check(rc, "resize_plain");
+    std::vector<Ciphertext> res(count);
+    for (size_t i = 0; i < count; ++i) {
+        res[i] = src[0];
+        detail::check(fhe_copy(res[i].ptr(), out.ptr() + i * ctw, ctw * 8, nullptr), "copy");
+    }
+    detail::check(fhe_stream_sync(nullptr), "sync");
+    return res;
+}
 }  // namespace hip
 
 }  // namespace seal

@@ -837,6 +837,127 @@ def server_filter(ctx, in_path, out_path, width, height, weights, anchor=None, s
 
 
 # ------------------------------------------------------------------------------------------------
+# server_resize_plain: a separable resize with public weights over a pixel stream
+# ------------------------------------------------------------------------------------------------
+def server_resize_plain(ctx, in_path, out_path, width, height, dst_w, dst_h, kernel="catmull_rom", antialias=False, convention="half_pixel",
+                        weight_bits=None, rows_per_step=4, validate=True, rows=None, io_threads=8, int_coeffs=100, frac_coeffs=100, stats=None):
+    """Resize an encrypted image to dst_w x dst_h with PUBLIC interpolation weights (circuits.resample_axis_plan; Evaluator.remap): plaintext
+    products and additions only, records stay at two polynomials.  The outputs are not the ciphertexts of server_resize (which encrypts the
+    offsets and multiplies ciphertexts); with kernel="reference_cubic", convention="reference" they decrypt to the same image.
+
+    Input stream: width * height pixels, row by row, three size-2 records (R, G, B) per pixel -- what client.send_resize writes.  Output
+    stream: dst_w * dst_h pixels in the same order -- what client.receive_pixels reads.  in_path / out_path: file names or open StreamFile
+    objects.  Returns the number of pixels produced.
+
+    A step produces up to `rows_per_step` destination rows.  Every source row is read once, checked (`validate`), and resampled
+    HORIZONTALLY once, straight into NTT form (remap with out_is_ntt); the resident window holds those dst_w-wide rows, and the step's
+    vertical pass reads them with src_is_ntt -- one forward and one inverse transform per ciphertext in all.  The rows the next step reads
+    again are moved to the front of the window.  The loop is synchronous, as server_filter's.
+
+    rows=(y0, y1) produces a SHARD of the destination rows at its own position of the output stream, reading only the source rows it
+    needs: processes with disjoint row ranges fill one output file without any exchange."""
+    import time
+    from . import circuits
+    from .evaluator import WeightTable
+    tx, wx = circuits.resample_axis_plan(width, dst_w, kernel, antialias, convention, weight_bits)
+    ty, wy = circuits.resample_axis_plan(height, dst_h, kernel, antialias, convention, weight_bits)
+    row0, row1 = (0, dst_h) if rows is None else (int(rows[0]), int(rows[1]))
+    if not (0 <= row0 < row1 <= dst_h):
+        raise ValueError("rows %r are not a range of the %d destination rows" % (rows, dst_h))
+    if rows_per_step < 1:
+        raise ValueError("rows_per_step must be positive")
+    vx, idx = circuits._weight_ids(wx)
+    vy, idy = circuits._weight_ids(wy)
+    table_x, table_y = WeightTable(ctx, vx, int_coeffs, frac_coeffs), WeightTable(ctx, vy, int_coeffs, frac_coeffs)
+    tx, ty = tx.astype(np.int64), ty.astype(np.int64)
+    ev = Evaluator(ctx)
+    residues = _ResidueCheck(ctx, validate)
+    rec = RECORD_HEADER + 2 * ctx.k * ctx.n * 8
+    own_in, own_out = not isinstance(in_path, StreamFile), not isinstance(out_path, StreamFile)
+    if (in_path.size if not own_in else os.path.getsize(in_path)) < width * height * 3 * rec:
+        raise EOFError("ciphertext stream ended")
+    steps = [(y, min(y + rows_per_step, row1)) for y in range(row0, row1, rows_per_step)]
+
+    def span(a, b):                                                                          # the source rows destination rows [a, b) read
+        live = wy[a:b] != 0.0
+        used = ty[a:b][live] if np.any(live) else ty[a:b]
+        return int(used.min()), int(used.max()) - int(used.min()) + 1
+
+    # The window only moves forwards (rows are read once and kept in stream order), but a step's own span need not: an output that samples
+    # exactly on a source row has weights 0, 1, 0, 0 and reads that row alone, while the next output reads the row before it again.  So a
+    # step's window starts at the smallest first row of this and every LATER step, and ends at the largest last row of this and every EARLIER one.
+    spans = [span(a, b) for a, b in steps]
+    firsts = np.minimum.accumulate(np.array([f for f, _ in spans])[::-1])[::-1]
+    lasts = np.maximum.accumulate(np.array([f + c for f, c in spans]))
+    spans = [(int(f), int(e - f)) for f, e in zip(firsts, lasts)]
+    max_rows = max(c for _, c in spans)
+    ch = np.arange(3, dtype=np.int64)
+    # horizontal pass over L freshly read lines: [L][width][3] -> [L][dst_w][3] (the first L * dst_w * 3 rows of these tables)
+    line = np.arange(max_rows, dtype=np.int64)
+    h_taps = ((line[:, None, None, None] * width + tx[None, :, None, :]) * 3 + ch[None, None, :, None]).reshape(-1, tx.shape[1]).astype(np.uint32)
+    h_wids = np.ascontiguousarray(np.broadcast_to(idx[None, :, None, :], (max_rows, dst_w, 3, tx.shape[1]))).reshape(-1, tx.shape[1])
+    col = np.arange(dst_w, dtype=np.int64)
+    shape = (2, ctx.k, ctx.n)
+    resident = torch.empty((max_rows, dst_w, 3) + shape, dtype=torch.int64, device=ctx.device)     # NTT form, horizontally resampled source rows [lo, hi)
+    fresh = torch.empty((max_rows, width, 3) + shape, dtype=torch.int64, device=ctx.device)        # a step's new rows as uploaded
+    hin = _pinned(("rsp_in",), (max_rows, width, 3) + shape)
+    max_px = rows_per_step * dst_w
+    hout = _pinned(("rsp_out",), (max_px, 3) + shape)
+    dout = torch.empty((max_px, 3) + shape, dtype=torch.int64, device=ctx.device)
+    fin = StreamFile(in_path) if own_in else in_path
+    fout = None
+    t0, seconds = time.perf_counter(), {"read": 0.0, "write": 0.0}
+    try:
+        fout = StreamFile(out_path, write=True, size=dst_w * dst_h * 3 * rec) if own_out else out_path
+        if fout.size < dst_w * dst_h * 3 * rec:
+            raise ValueError("output stream file is smaller than the result")
+        lo = hi = spans[0][0]                                                                # resident source rows [lo, hi)
+        for (y0, y1), (first, cnt) in zip(steps, spans):
+            keep_from = min(max(first, lo), hi)
+            keep = hi - keep_from
+            if keep and keep_from > lo:
+                resident[:keep].copy_(resident[keep_from - lo:hi - lo].clone())
+            lo = first if keep == 0 else keep_from
+            new_first, new_cnt = lo + keep, first + cnt - (lo + keep)
+            if new_cnt > 0:
+                t_io = time.perf_counter()
+                fin.transfer(new_first * width * 3, new_cnt * width * 3, 2, ctx, hin, io_threads)
+                seconds["read"] += time.perf_counter() - t_io
+                fresh[:new_cnt].copy_(hin[:new_cnt], non_blocking=True)
+                residues.add(fresh[:new_cnt])
+                ev.remap(table_x, fresh[:new_cnt].view(-1, *shape), h_taps[:new_cnt * dst_w * 3], h_wids[:new_cnt * dst_w * 3],
+                         out=resident[keep:keep + new_cnt].view(-1, *shape), out_is_ntt=True)
+            hi = first + cnt
+            if lo != first or hi - lo > max_rows:
+                raise RuntimeError("server_resize_plain: resident window [%d, %d) does not match the step's source rows [%d, +%d)" % (lo, hi, first, cnt))
+            rel = ty[y0:y1] - lo
+            if np.any((wy[y0:y1] != 0.0) & ((rel < 0) | (rel >= hi - lo))):
+                raise RuntimeError("server_resize_plain: destination rows [%d, %d) read outside the resident window" % (y0, y1))
+            rel = np.clip(rel, 0, hi - lo - 1)                                               # slots of weight zero may name a row outside the window: never read
+            v_taps = ((rel[:, None, None, :] * dst_w + col[None, :, None, None]) * 3 + ch[None, None, :, None]).reshape(-1, ty.shape[1])
+            v_wids = np.ascontiguousarray(np.broadcast_to(idy[y0:y1, None, None, :], (y1 - y0, dst_w, 3, ty.shape[1]))).reshape(-1, ty.shape[1])
+            npx = (y1 - y0) * dst_w
+            ev.remap(table_y, resident[:hi - lo].view(-1, *shape), v_taps, v_wids, out=dout[:npx].view(-1, *shape), src_is_ntt=True)
+            hout[:npx].copy_(dout[:npx], non_blocking=True)
+            torch.cuda.current_stream().synchronize()                                        # hin may be refilled, hout has landed
+            t_io = time.perf_counter()
+            fout.transfer(y0 * dst_w * 3, npx * 3, 2, ctx, hout, io_threads)
+            seconds["write"] += time.perf_counter() - t_io
+        residues.verdict(_refuser(own_out, fout, out_path))
+        if stats is not None:
+            stats.update(seconds=time.perf_counter() - t0, steps=len(steps), file_read_seconds=seconds["read"], file_write_seconds=seconds["write"],
+                         resident_rows=max_rows, dst_w=dst_w, dst_h=dst_h, taps=(int(tx.shape[1]), int(ty.shape[1])),
+                         distinct_weights=(table_x.distinct, table_y.distinct))
+    finally:
+        torch.cuda.synchronize()
+        if own_in:
+            fin.close()
+        if own_out and fout is not None:
+            fout.close()
+    return (row1 - row0) * dst_w
+
+
+# ------------------------------------------------------------------------------------------------
 # server_decode: the run-length decoder's driver loop (homo/server_decode.cpp:113-148) over a ciphertext stream
 # ------------------------------------------------------------------------------------------------
 def make_zero_encryptor(ctx, public_key, encoder=None, seed=None, indexed=False, device=None):

@@ -79,7 +79,8 @@ const char *fhe_last_error(void);
  *      evaluator.relinearize, as SEAL's does), fhe_circuits_create_relin_at (include/fhe_circuits.h: where the relinearised mode
  *      relinearises); fhe_relinearize_to rejects partially overlapping input / output ranges.  Version 4 also carries
  *      fhe_idct_plan_create / destroy, fhe_idct8x8_scratch_bytes, fhe_idct8x8_dequant and fhe_ycc_to_rgb_blocks, added later:
- *      new entry points only, no existing signature or contract changed.  The same holds for the fhe_filter_* entry points (2-D convolution).
+ *      new entry points only, no existing signature or contract changed.  The same holds for the fhe_filter_* entry points (2-D convolution)
+ *      and for fhe_weight_table_*, fhe_remap* and fhe_resample_axis_plan (resampling with public weights).
  * A host compiled against this header compares fhe_abi_version() with FHE_ABI_VERSION before anything else (the Python
  * binding and seal/seal.h do). */
 #define FHE_ABI_VERSION 4
@@ -407,6 +408,81 @@ int fhe_filter2d(const fhe_ctx *ctx, const fhe_filter_plan *plan, const uint64_t
  * in one kernel), 0 = the general path k_filter_mac + fhe_ntt_inverse on Shoup arithmetic, 4 = the general path with the transforms
  * on the exact-FP64 kernels (where fhe_ntt_forward runs them: n = 4096, primes <= 40 bits). */
 int fhe_filter_path(const fhe_ctx *ctx);
+
+/* ---- resampling with public weights on encrypted pixels: resize by any factor, rotate, warp ---------------
+ * Where a pixel of the output lies in the source depends on the image dimensions (or the warp) alone, so the interpolation weights
+ * are PUBLIC: resampling is a linear map with plaintext weights, multiply_plain and add only.  (The reference's SampleBicubic /
+ * SampleLinear encrypt the offsets and multiply ciphertext by ciphertext: fhe_resize_bicubic_shared in include/fhe_circuits.h.)
+ * fhe_remap is fhe_filter2d with the weights chosen PER OUTPUT.  A weight table holds the plaintexts; output o names, slot by slot, a
+ * source ciphertext taps[o][p] and a table entry wids[o][p].  Specification of output o for tables of T slots per output:
+ *     acc = none
+ *     for p in 0 .. T - 1, in this order:
+ *         if wids[o][p] == FHE_REMAP_SKIP or encode(w[wids[o][p]]) is the zero plaintext: continue
+ *         term = multiply_plain(src[taps[o][p]], encode(w[wids[o][p]]))     (encode = FractionalEncoder(int_coeffs, frac_coeffs, base 2))
+ *         acc  = term if acc is none else add(acc, term)
+ *     out[o] = acc                                                          (`size` polynomials, fully reduced)
+ * fhe_remap gives exactly these bits with ONE forward transform per source polynomial and ONE inverse transform per output polynomial
+ * (csrc/resample.hip).  Plaintext products only: no auxiliary base, the ciphertext size stays what it was, every context
+ * fhe_ctx_create accepts is supported.
+ *
+ * Weight table: each DISTINCT value (compared as doubles) is encoded, lifted and transformed once and kept on the device in the one
+ * form the context's kernels read: k * n * 8 bytes per distinct entry on the pseudo-Mersenne paths (fhe_remap_path 1 / 2), k * n * 16
+ * bytes (Shoup pairs) otherwise -- 256 KiB and 192 KiB per entry at P8192 and P4096.  Entries that encode to the zero plaintext take no
+ * device memory and are remembered as such (their slots are skipped, as the specification says).  A value the encoder cannot hold, a
+ * value that is not finite, count == 0 and more than FHE_REMAP_MAX_WEIGHTS distinct non-zero entries are refused.  A table belongs to
+ * the context it was created with. */
+#define FHE_REMAP_MAX_TAPS 64        /* slots per output */
+#define FHE_REMAP_MAX_WEIGHTS 4096   /* distinct non-zero entries of one table (1 GiB at P8192) */
+#define FHE_REMAP_SKIP 0xffffffffu   /* wids[o][p]: slot p of output o is unused */
+typedef struct fhe_weight_table fhe_weight_table;
+int fhe_weight_table_create(const fhe_ctx *ctx, const double *weights, uint32_t count, int int_coeffs, int frac_coeffs, fhe_stream stream,
+                            fhe_weight_table **out);
+int fhe_weight_table_destroy(fhe_weight_table *table);
+/* entries (what wids index), and distinct entries held on the device */
+int fhe_weight_table_count(const fhe_weight_table *table);
+int fhe_weight_table_distinct(const fhe_weight_table *table);
+/* src: [n_src][size][k][n] device memory, never written.  out: [count][size][k][n], must not overlap src.  taps, wids: HOST memory,
+ * [count][T], consumed before the call returns; 1 <= T <= FHE_REMAP_MAX_TAPS.  src_is_ntt != 0: src already holds what fhe_ntt_forward
+ * writes (canonical values), no forward pass runs and no scratch is needed; otherwise scratch holds the transformed sources
+ * (fhe_remap_scratch_bytes = n_src * size * k * n * 8).  out_is_ntt != 0: the call stores the canonical slot-form sum -- exactly what
+ * fhe_ntt_forward of the specified output would write -- and no inverse transform runs; a second fhe_remap takes that buffer with
+ * src_is_ntt, so the two passes of a separable resize cost one transform pair per ciphertext, not two.  Everything is checked before
+ * anything is enqueued, and a refused call writes nothing: an output without a live term (every slot skipped or a zero plaintext), a
+ * tap >= n_src or a weight id >= fhe_weight_table_count in a slot that is not skipped, T out of range, size == 0, a table of another
+ * context, out overlapping src, short or overlapping scratch: FHE_ERR_PARAM.  count == 0 is a no-op. */
+size_t fhe_remap_scratch_bytes(const fhe_ctx *ctx, const fhe_weight_table *table, uint32_t size, uint64_t n_src, uint64_t count, int src_is_ntt);
+int fhe_remap(const fhe_ctx *ctx, const fhe_weight_table *table, const uint64_t *src, uint64_t n_src, uint32_t size, int src_is_ntt,
+              const uint32_t *taps, const uint32_t *wids, uint32_t T, uint64_t *out, int out_is_ntt, uint64_t count, void *scratch,
+              size_t scratch_bytes, fhe_stream stream);
+/* which kernels fhe_remap launches after the forward transforms: 1 / 2 = k_remap_acc_pm on the pseudo-Mersenne class 1 / 2 of the
+ * q-base (gather, lazy sums, products and -- unless out_is_ntt -- the inverse transform in one kernel), 0 = the general path
+ * k_remap_mac (+ fhe_ntt_inverse) on Shoup arithmetic, 4 = the general path with the transforms on the exact-FP64 kernels. */
+int fhe_remap_path(const fhe_ctx *ctx);
+
+/* Index and weight arithmetic of ONE axis of a separable resize (host only, no context, callable without a device).  Writes
+ * taps, weights: [dst_len][T]; both NULL only reports T.  Output x samples the source at u and reads T = 2 c consecutive positions
+ * floor(u) - c + 1 .. floor(u) + c, clamped to the edge, c = ceil(radius * s): radius 1 (triangle), 2 (the cubics), 3 (Lanczos-3),
+ * 1/2 (box); s = src_len / dst_len if antialias != 0 and src_len > dst_len (the kernel is stretched over the samples an output
+ * covers), else 1.  The weight of position j is kernel((j - u) / s); the weights of one output are divided by their sum; with
+ * weight_bits > 0 (at most 30) each is then rounded to a multiple of 2^-weight_bits (floor(w 2^bits + 1/2)) and what the sum lacks
+ * to 1 is added to the largest (the first of equals), so the sum is exactly 1.  A plan of more than FHE_REMAP_MAX_TAPS taps is refused.
+ * Kernels: TRIANGLE 1 - |d|;  CATMULL_ROM, the cubic of homo/fhe_resize.h:150-185 with a true t^3: weights (-t^3 + 2t^2 - t) / 2,
+ * (3t^3 - 5t^2 + 2) / 2, (-3t^3 + 4t^2 + t) / 2, (t^3 - t^2) / 2 at offset t;  REFERENCE_CUBIC, the same polynomial with the
+ * reference's t3 = t * t (:174-175): weights (t^2 - t) / 2, 1 - t^2, (t^2 + t) / 2, 0 -- what the ct x ct circuit computes;
+ * LANCZOS3 sinc(d) sinc(d / 3) for |d| < 3;  BOX 1 on [-1/2, 1/2).
+ * Conventions: HALF_PIXEL u = (x + 0.5) src_len / dst_len - 0.5 in double; with src_len == dst_len the plan is the identity, T = 1.
+ * REFERENCE u = float(x) / float(dst_len - 1) * float(src_len) - 0.5 stored as float (homo/fhe_resize.h:351,382; dst_len >= 2),
+ * first position int(u) - c + 1 (int() rounds towards zero, :228,260) and offset u - floor(u) (:230,262): the positions and offsets
+ * of fhe_resize_sample_plan. */
+#define FHE_RESAMPLE_TRIANGLE 0
+#define FHE_RESAMPLE_CATMULL_ROM 1
+#define FHE_RESAMPLE_REFERENCE_CUBIC 2
+#define FHE_RESAMPLE_LANCZOS3 3
+#define FHE_RESAMPLE_BOX 4
+#define FHE_RESAMPLE_HALF_PIXEL 0
+#define FHE_RESAMPLE_REFERENCE 1
+int fhe_resample_axis_plan(uint32_t src_len, uint32_t dst_len, int kernel, int antialias, int convention, int weight_bits, uint32_t *T,
+                           uint32_t *taps, double *weights);
 
 /* ---- server-side encryptions (round 5) ------------------------------------------------------------
  * The reference's servers ENCRYPT inside their loops: SampleLinear / SampleBicubic encrypt frac(x) and frac(y) for every output
