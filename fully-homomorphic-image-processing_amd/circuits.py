@@ -566,3 +566,45 @@ def decode_channel(ev, pc, runs, index, acc0, zeros, order, degree, delta, width
     _lib.call("fhe_decode_channel_range", cc.h, _ptr(runs) if pairs else null, pairs, _ptr(index), _ptr(acc0),
               _ptr(zeros) if (pairs and degree > 0) else null, order, degree, float(delta), width, height, p0, p1, _ptr(out), _ptr(scr), nbytes, _stream())
     return out
+
+
+# ---- packed images: one ciphertext holds a tile of pixels in its slots (client.BatchEncoder), a filter is rotations of it -------------
+def packed_filter_valid_mask(n, tile_w, kw, kh, anchor=None):
+    """[n] bool, flat slot order: where packed_filter2d's window stays inside its tile (each of the two rows of n/2 slots holds one
+    row-major tile of tile_w x tile_h pixels) -- everywhere else the rotation wrapped around the row and the value is not the filter's"""
+    ax, ay = filter_anchor(kw, kh) if anchor is None else anchor
+    half = n // 2
+    if tile_w <= 0 or half % tile_w:
+        raise ValueError("packed tiles: tile_w = %d does not divide the row of %d slots" % (tile_w, half))
+    tile_h = half // tile_w
+    y, x = np.divmod(np.arange(half), tile_w)
+    ok = (x - ax >= 0) & (x + (kw - 1 - ax) < tile_w) & (y - ay >= 0) & (y + (kh - 1 - ay) < tile_h)
+    return np.concatenate([ok, ok])
+
+
+def packed_filter2d(ev, keys, ct, tile_w, weights_int, kw, kh, anchor=None):
+    """2-D filter with public INTEGER weights over packed tiles: ct [..., 2, k, n] holds, in each row of n/2 slots, a row-major tile of
+    tile_w x tile_h pixels.  Output = sum over the taps p = (i, j), row-major over the kernel with x fastest, of
+        multiply_plain(rotate_rows(ct, (j - ay) tile_w + (i - ax)), [w_p mod t])
+    with zero weights skipped: slot (y, x) of the result is sum_j,i w[j][i] pixel[y + j - ay][x + i - ax] modulo t, exactly, wherever the
+    window does not leave the tile (packed_filter_valid_mask); fixed point is the caller's choice of integers, clamp-to-edge is the
+    client's padding of the tile.  keys: GaloisKeys (rotations they do not hold directly run as hops, Evaluator.rotate_rows)."""
+    ctx = ev.ctx
+    ax, ay = filter_anchor(kw, kh) if anchor is None else anchor
+    w = [int(v) for v in np.asarray(weights_int).reshape(-1)]
+    if len(w) != kw * kh:
+        raise ValueError("packed_filter2d: %d weights for a %d x %d kernel" % (len(w), kw, kh))
+    if (ctx.n // 2) % tile_w:
+        raise ValueError("packed_filter2d: tile_w = %d does not divide the row of %d slots" % (tile_w, ctx.n // 2))
+    acc = None
+    for p, wp in enumerate(w):
+        if wp % ctx.t == 0:
+            continue
+        j, i = divmod(p, kw)
+        steps = (j - ay) * tile_w + (i - ax)
+        rot = ev.rotate_rows(ct, steps, keys) if ev.rotation_plan(steps, keys) else ct
+        term = ev.multiply_plain(rot, np.array([wp % ctx.t], dtype=np.uint64))
+        acc = term if acc is None else ev.add(acc, term, out=acc)
+    if acc is None:
+        raise ValueError("packed_filter2d: every weight is zero modulo t")
+    return acc

@@ -324,3 +324,44 @@ def receive_decode(ctx, decryptor, encoder, in_path, width, height, clamp=True, 
     """homo/client_decode.cpp:157-214: the decoded image, uint8 [height, width, 3] (position-major, channels interleaved:
     the order homo/server_decode.cpp:139-143 saves)"""
     return receive_pixels(ctx, decryptor, encoder, in_path, width, height, clamp, decoded)
+
+
+class BatchEncoder:
+    """seal::PolyCRTBuilder: n integers modulo t in the slots of one plaintext (include/fhe_hip.h "batched plaintext slots": t prime,
+    t = 1 mod 2n; two rows of n/2 slots, flat order row 0 then row 1).  encode() feeds DeviceEncryptor.encrypt_plains, decode() reads
+    Decryptor.decrypt_batch; the transforms modulo t run on the host (fhe_batch_encode / fhe_batch_decode)."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.slot_count = ctx.n
+        probe = np.zeros(ctx.n, dtype=np.uint64)
+        self._run("fhe_batch_encode", probe[None])                     # refuses a plain modulus without slots here, not at the first use
+
+    def _run(self, name, rows):
+        import ctypes as C
+        from . import _lib
+        src = np.ascontiguousarray(rows, dtype=np.uint64)
+        if src.ndim != 2 or src.shape[1] != self.ctx.n:
+            raise ValueError("%s: expected [count, n = %d] values, got %r" % (name, self.ctx.n, src.shape))
+        out = np.zeros_like(src)
+        _lib.call(name, self.ctx.n, self.ctx.t, src.ctypes.data_as(C.c_void_p), src.shape[0], out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def encode_host(self, slots):
+        """[count, n] (or [n]) slot values below t -> plaintext coefficients, numpy uint64 of the same shape"""
+        a = np.asarray(slots)
+        return self._run("fhe_batch_encode", a[None])[0] if a.ndim == 1 else self._run("fhe_batch_encode", a)
+
+    def encode(self, slots):
+        """[count, n] slot values -> [count, n] device tensor of plaintext coefficients (DeviceEncryptor.encrypt_plains takes it)"""
+        import torch
+        a = np.asarray(slots)
+        plain = self._run("fhe_batch_encode", a[None] if a.ndim == 1 else a)
+        return torch.from_numpy(plain.view(np.int64)).to(self.ctx.device)
+
+    def decode(self, plains):
+        """[count, n] (or [n]) plaintext coefficients (Decryptor.decrypt_batch's result, or a device tensor) -> slot values, numpy uint64"""
+        if hasattr(plains, "detach"):
+            plains = plains.detach().cpu().contiguous().numpy().view(np.uint64)
+        a = np.asarray(plains)
+        return self._run("fhe_batch_decode", a[None])[0] if a.ndim == 1 else self._run("fhe_batch_decode", a)

@@ -1656,3 +1656,21 @@ extern "C" int fhe_relinearize_poly(const fhe_ctx *cc, const uint64_t *ct3, uint
     KERNEL_CHECK();
     return FHE_OK;
 }
+
+// Pieces of the key switch for galois.hip, whose kernels read the source polynomials through an automorphism: whether the
+// pseudo-Mersenne kernels run for one key switch of this batch, the accumulation against the key (k_relin_accum_pm / k_relin_accum,
+// unchanged) and the q-base transforms of the general path.  The caller has run fhe_behz_ensure.
+bool fhe_relin_pm_ok(const fhe_ctx *c, u32 nd, u64 count) { return relin_pm_ok(c, nd, 1, count); }
+int fhe_qbase_ntt(bool inverse, const fhe_ctx *c, const u64 *in, u64 *out, u64 n_rns, hipStream_t st) { return qbase_ntt(inverse, c, in, out, n_rns, st); }
+int fhe_relin_accum(const fhe_ctx *c, const u64 *dig, const u64 *evk, u64 *acc, u32 nd, u64 count, hipStream_t st) {
+    const u32 k = c->k, n = c->n;
+    if (relin_pm_ok(c, nd, 1, count)) {
+        const RnsBase base = c->qb.dev();
+        if (c->qb.pm_class == 1) k_relin_accum_pm<PmA><<<grid2(n, count * k), 256, 0, st>>>(dig, evk, acc, base, n, nd, count, 1);
+        else k_relin_accum_pm<PmB><<<grid2(n, count * k), 256, 0, st>>>(dig, evk, acc, base, n, nd, count, 1);
+    } else {
+        k_relin_accum<<<grid2(n, count * k), 256, 0, st>>>(dig, evk, acc, c->behz->dev, n, nd, count);
+    }
+    KERNEL_CHECK();
+    return FHE_OK;
+}

@@ -244,6 +244,8 @@ extern "C" int fhe_ctx_create(uint32_t n, const uint64_t *q, uint32_t k, uint64_
         if (const char *e = getenv("FHE_DCT_ONE_LAUNCH")) o.dct_one_launch = (u32)atoi(e);
         o.relin_fused = env_on("FHE_RELIN_FUSED");
         o.filter_xcd = !off("FHE_FILTER_XCD");
+        o.galois_staged = env_on("FHE_GALOIS_STAGED");
+        o.galois_gather_lds = env_on("FHE_GALOIS_GATHER_LDS");
         o.relin_steps = env_on("FHE_RELIN_STEPS");
         o.enc_unfused = env_on("FHE_ENC_UNFUSED");
         { const char *e = std::getenv("FHE_ENC_OCC"); o.enc_occ4 = e && e[0] == '4'; }

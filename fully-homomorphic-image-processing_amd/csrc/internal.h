@@ -68,6 +68,8 @@ struct FheOptions {
     bool relin_fused = false;        // FHE_RELIN_FUSED=1 (experiment, round 5): key-switch accumulation inside the inverse-transform kernel (k_relin_accum_inv_add_pm: one launch and
                                      // 4 MB of traffic per relinearisation less, same bits, 1-3 % SLOWER at dbc = 30 -- the digits are read twice and the kernels are issue-bound; profiles/EXPERIMENTS.md)
     bool filter_xcd = true;          // FHE_FILTER_XCD=0: fhe_filter2d hands its workgroups out in plain order (every eighth output per XCD) instead of one contiguous run of outputs per XCD
+    bool galois_staged = false;      // FHE_GALOIS_STAGED=1: fhe_apply_galois writes [sigma(c0), 0, sigma(c1)] to scratch and runs the plain key switch on it (galois.hip: the correctness baseline)
+    bool galois_gather_lds = false;  // FHE_GALOIS_GATHER_LDS=1: the fused digit kernel reads sigma(c1) with coalesced loads into LDS + permuted LDS reads instead of permuted global loads (measured 2-4 % slower at P8192)
     bool behz_fused_prepare = false; // FHE_BEHZ_FUSED_PREPARE=1: base extension fused into the forward transforms (k_behz_prepare_pm: 25 % less HBM traffic per
                                      // product, 5 % slower -- the y_i are recomputed per auxiliary prime and the kernels are issue-bound; profiles/EXPERIMENTS.md)
 };
@@ -181,6 +183,10 @@ int fhe_behz_tensor_shared(const fhe_ctx *c, const u64 *a, u32 sa, const u64 *bp
 int fhe_behz_floor3_combine(const fhe_ctx *c, const u64 *da, const u64 *db, const u64 *dc, u32 size_ab, u32 size_c, const u64 *B, CMap mB, u32 size_b,
                             u64 *out, CMap mo, u64 count, hipStream_t st);   // thread-safe: builds the ct x ct tables on first use; later calls cost one atomic load
 void fhe_behz_free(fhe_ctx *c);
+// key-switch pieces shared with galois.hip (behz.hip, at the end): the caller has run fhe_behz_ensure
+bool fhe_relin_pm_ok(const fhe_ctx *c, u32 nd, u64 count);
+int fhe_relin_accum(const fhe_ctx *c, const u64 *dig, const u64 *evk, u64 *acc, u32 nd, u64 count, hipStream_t st);
+int fhe_qbase_ntt(bool inverse, const fhe_ctx *c, const u64 *in, u64 *out, u64 n_rns, hipStream_t st);
 // fused FP64 DCT path (dct_fused.hip)
 bool fhe_dct_f64_supported(const fhe_ctx *c);
 // which: bit 0 = row kernel, bit 1 = column kernel

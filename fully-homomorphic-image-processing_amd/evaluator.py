@@ -508,6 +508,80 @@ class Evaluator:
         _lib.call("fhe_relinearize_n", self.ctx.h, _ptr(work), size, size * kn, _ptr(out), 2 * kn, count, _ptr(evk_ntt), dbc, _ptr(scr), nbytes, _stream())
         return out
 
+    # -- seal::Evaluator::rotate_rows / rotate_columns (include/fhe_hip.h: batched slots and Galois rotations) --------
+    def _galois_key(self, keys, g, who):
+        """the key tensor for element g, refused when the key set belongs to a context of other shapes (the library would read it with
+        THIS context's strides) or does not hold the digits of its own dbc"""
+        kc = keys.ctx
+        if (kc.n, kc.k, kc.device) != (self.ctx.n, self.ctx.k, self.ctx.device) or list(kc.q) != list(self.ctx.q):
+            raise ValueError("%s: Galois keys of another context (n = %d, k = %d on %s; this one has n = %d, k = %d on %s)"
+                             % (who, kc.n, kc.k, kc.device, self.ctx.n, self.ctx.k, self.ctx.device))
+        key = keys.key(g)
+        check_evaluation_keys(self.ctx, key, keys.dbc, 1, who)
+        return key
+
+    def apply_galois(self, a, g, keys, out=None):
+        """sigma_g on a batch of size-2 ciphertexts followed by the key switch back to s (fhe_apply_galois): keys = GaloisKeys holding g.
+        `out` may be `a` itself (in place) or a contiguous tensor of the same shape that does not overlap it."""
+        g = int(g)
+        if a.dim() < 3 or a.shape[-3] != 2 or tuple(a.shape[-2:]) != (self.ctx.k, self.ctx.n):
+            raise ValueError("apply_galois: ciphertexts of size 2 of this context only (SEAL 2.3 refuses other sizes: relinearize first), got %r" % (tuple(a.shape),))
+        if not (g & 1) or not 1 < g < 2 * self.ctx.n:
+            raise ValueError("apply_galois: Galois element %d must be odd and in (1, 2n = %d)" % (g, 2 * self.ctx.n))
+        key = self._galois_key(keys, g, "apply_galois")
+        if out is not None and (tuple(out.shape) != tuple(a.shape) or out.dtype != a.dtype or not out.is_contiguous() or out.device != a.device):
+            raise ValueError("apply_galois: `out` must be a contiguous int64 tensor of shape %r on the input's device" % (tuple(a.shape),))
+        out = torch.empty_like(a) if out is None else out
+        ctw = 2 * self.ctx.k * self.ctx.n
+        count = self._npolys(a) // 2
+        nbytes = _lib.load().fhe_apply_galois_scratch_bytes(self.ctx.h, keys.dbc, count)
+        scr = self._scratch_buf(nbytes)
+        _lib.call("fhe_apply_galois", self.ctx.h, _ptr(a), ctw, _ptr(out), ctw, count, g, _ptr(key), keys.dbc, _ptr(scr), nbytes, _stream())
+        return out
+
+    def rotation_plan(self, steps, keys):
+        """the Galois elements rotate_rows(ct, steps, keys) applies, in order: steps are reduced into (-n/4, n/4]; one element if `keys`
+        holds 3^steps mod 2n, otherwise the hops 3^(+-2^i) for the set bits i of |steps|, ascending; [] for steps == 0"""
+        n = self.ctx.n
+        half = n // 2
+        s = int(steps) % half
+        if s > half // 2:
+            s -= half
+        if s == 0:
+            return []
+        g = self._gal_elt(s)
+        if keys.has(g):
+            return [g]
+        sign = 1 if s > 0 else -1
+        return [self._gal_elt(sign * (1 << i)) for i in range(abs(s).bit_length()) if (abs(s) >> i) & 1]
+
+    def _gal_elt(self, steps, swap=False):
+        g = C.c_uint32()
+        _lib.call("fhe_galois_element", self.ctx.n, int(steps), int(swap), C.byref(g))
+        return int(g.value)
+
+    def rotate_rows(self, a, steps, keys, out=None):
+        """both rows of slots rotated LEFT by `steps` (negative: right): slot (r, j) of the result is slot (r, j + steps mod n/2) of `a`"""
+        plan = self.rotation_plan(steps, keys)
+        if not plan:                                                   # a copy, under the checks apply_galois makes
+            if a.dim() < 3 or a.shape[-3] != 2 or tuple(a.shape[-2:]) != (self.ctx.k, self.ctx.n):
+                raise ValueError("rotate_rows: ciphertexts of size 2 of this context only, got %r" % (tuple(a.shape),))
+            if out is None:
+                return a.clone()
+            if tuple(out.shape) != tuple(a.shape) or out.dtype != a.dtype or not out.is_contiguous() or out.device != a.device:
+                raise ValueError("rotate_rows: `out` must be a contiguous int64 tensor of shape %r on the input's device" % (tuple(a.shape),))
+            if out is not a:
+                out.copy_(a)
+            return out
+        cur = a
+        for g in plan:
+            cur = out = self.apply_galois(cur, g, keys, out=out)       # the first hop writes `out`, the others run in place on it
+        return out
+
+    def rotate_columns(self, a, keys, out=None):
+        """the two rows of slots swapped (g = 2n - 1)"""
+        return self.apply_galois(a, 2 * self.ctx.n - 1, keys, out=out)
+
     # -- primitives named by the north star ---------------------------------------------------------
     def cubic_coeffs(self, A, B, C, D):
         """a = 3B - A - 3C + D, b = 2A - 5B + 4C - D, c = C - A of Cubic (homo/fhe_resize.h:150-172) in one

@@ -121,27 +121,106 @@ class KeyGenerator:
         keys)): [count][k][digits][2][k][n], the keys for s^2 .. s^(count+1) -- what relinearising a ciphertext of count + 2
         polynomials takes (Circuits(relin=(keys, dbc, "cubic")): count = 2)."""
         ctx = self.ctx
-        nd = int(_lib.load().fhe_evk_digits(ctx.h, dbc))
         out = []
         power = self._sk                                                        # s^j, coefficient form [1, k, n]
         for _ in range(count):
             power = _ring_mul(ctx, power, self._sk_ntt)
-            sp = to_host(power)[0]
-            evk = np.zeros((ctx.k, nd, 2, ctx.k, ctx.n), dtype=np.uint64)
-            for i in range(ctx.k):
-                for d in range(nd):
-                    a = self._smp.uniform()
-                    e = to_device(self._smp.noise()[None], ctx.device)
-                    k0 = _ring_mul(ctx, to_device(a[None], ctx.device), self._sk_ntt)
-                    _lib.call("fhe_add", ctx.h, _ptr(k0), _ptr(e), _ptr(k0), 1, _stream())
-                    _lib.call("fhe_negate", ctx.h, _ptr(k0), _ptr(k0), 1, _stream())
-                    h0 = to_host(k0)[0].copy()
-                    qi = ctx.q[i]
-                    wd = pow(2, dbc * d, qi)
-                    h0[i] = np.array([(int(x) + int(s) * wd) % qi for x, s in zip(h0[i], sp[i])], dtype=np.uint64)
-                    evk[i, d, 0], evk[i, d, 1] = h0, a
-            out.append(_ntt(ctx, to_device(evk, ctx.device)))
+            out.append(self._switch_key(to_host(power)[0], dbc))
         return out[0] if count == 1 else torch.stack(out).contiguous()
+
+    def _switch_key(self, target, dbc):
+        """[k][digits][2][k][n] in NTT form: the key that switches a polynomial multiplying `target` ([k, n] host residues, coefficient
+        form) back to s: entry (i, d) = (-(a s + e) + 2^(dbc d) target on component i only, a)"""
+        ctx = self.ctx
+        nd = int(_lib.load().fhe_evk_digits(ctx.h, dbc))
+        evk = np.zeros((ctx.k, nd, 2, ctx.k, ctx.n), dtype=np.uint64)
+        for i in range(ctx.k):
+            for d in range(nd):
+                a = self._smp.uniform()
+                e = to_device(self._smp.noise()[None], ctx.device)
+                k0 = _ring_mul(ctx, to_device(a[None], ctx.device), self._sk_ntt)
+                _lib.call("fhe_add", ctx.h, _ptr(k0), _ptr(e), _ptr(k0), 1, _stream())
+                _lib.call("fhe_negate", ctx.h, _ptr(k0), _ptr(k0), 1, _stream())
+                h0 = to_host(k0)[0].copy()
+                qi = ctx.q[i]
+                wd = pow(2, dbc * d, qi)
+                h0[i] = np.array([(int(x) + int(s) * wd) % qi for x, s in zip(h0[i], target[i])], dtype=np.uint64)
+                evk[i, d, 0], evk[i, d, 1] = h0, a
+        return _ntt(ctx, to_device(evk, ctx.device))
+
+    def generate_galois_keys(self, dbc, elements=None):
+        """seal::KeyGenerator::generate_galois_keys: one key-switching key per Galois element g, for the target sigma_g(s), in the form
+        and digit rule of generate_evaluation_keys.  elements=None: {3^(+-2^i) mod 2n : 0 <= i < log2(n/2)} and 2n - 1 -- every row
+        rotation is then at most log2(n/4) + 1 hops (Evaluator.rotate_rows), the column swap one."""
+        ctx = self.ctx
+        if elements is None:
+            elements = default_galois_elements(ctx.n)
+        sk = to_host(self._sk)[0]
+        keys = {}
+        for g in elements:
+            g = int(g)
+            if g in keys:
+                continue
+            if not (g & 1) or not 1 < g < 2 * ctx.n:
+                raise ValueError("Galois element %d: must be odd and in (1, 2n = %d)" % (g, 2 * ctx.n))
+            keys[g] = self._switch_key(apply_galois_host(sk, g, ctx.q), dbc)
+        return GaloisKeys(ctx, dbc, keys)
+
+
+def galois_element(n, steps=0, swap_rows=False):
+    """the Galois element of a row rotation LEFT by `steps` slots (negative: right), times 2n - 1 with swap_rows (fhe_galois_element)"""
+    g = C.c_uint32()
+    _lib.call("fhe_galois_element", int(n), int(steps), int(bool(swap_rows)), C.byref(g))
+    return int(g.value)
+
+
+def default_galois_elements(n):
+    out, i = [], 0
+    while (1 << i) < n // 2:
+        out += [galois_element(n, 1 << i), galois_element(n, -(1 << i))]
+        i += 1
+    return out + [2 * n - 1]
+
+
+def apply_galois_host(a, g, q):
+    """sigma_g of [k, n] residues on the host (x^i -> x^(i g mod 2n), x^n = -1): what the Galois key's target sigma_g(s) is made with"""
+    n = a.shape[-1]
+    e = (np.arange(n, dtype=np.int64) * int(g)) % (2 * n)
+    out = np.zeros_like(a)
+    for i, qi in enumerate(q):
+        neg = np.where(a[i] == 0, np.uint64(0), np.uint64(qi) - a[i])
+        out[i, e % n] = np.where(e >= n, neg, a[i])
+    return out
+
+
+class GaloisKeys:
+    """seal::GaloisKeys: Galois element -> key-switching key (device tensor [k][digits][2][k][n], NTT form), and the decomposition
+    bit count they were made with.  Belongs to the context that generated it."""
+
+    def __init__(self, ctx, dbc, keys):
+        self.ctx, self.dbc, self._keys = ctx, int(dbc), dict(keys)
+
+    def has(self, g):
+        return int(g) in self._keys
+
+    def elements(self):
+        return sorted(self._keys)
+
+    def save(self, f):
+        """the record seal::hip::GaloisKeys::load reads (seal/seal.h): magic, u32 dbc, digits, count, k, n, reserved, then per element (ascending)
+        u32 element, u32 reserved and the key's words"""
+        import struct
+        ctx = self.ctx
+        digits = int(_lib.load().fhe_evk_digits(ctx.h, self.dbc))
+        f.write(b"FHEHIPG\0" + struct.pack("<6I", self.dbc, digits, len(self._keys), ctx.k, ctx.n, 0))
+        for g in self.elements():
+            f.write(struct.pack("<2I", g, 0))
+            f.write(to_host(self._keys[g]).tobytes())
+
+    def key(self, g):
+        if int(g) not in self._keys:
+            raise ValueError("no Galois key for element %d (have %r)" % (g, self.elements()))
+        return self._keys[int(g)]
 
 
 class Encryptor:

@@ -10,6 +10,9 @@
 //   seal::hip::Circuits          one fhe_circuits handle + scratch: cubic, linear, sample_bicubic, sample_linear,
 //                                resize_bicubic (shared offsets), homomorphic_sin / _cos, approximated_step, decode_channel
 //
+// (The slot encoder and the Galois rotations -- seal::hip::batch_encode / batch_decode, GaloisKeys, generate_galois_keys, apply_galois,
+// rotate_rows, rotate_columns -- work on std::vector<seal::Ciphertext> and live in seal/seal.h, beside filter2d and remap.)
+//
 // Each method is one library call: the taps are index arrays, every temporary lives in the handle's scratch buffer, no
 // per-ciphertext work happens on the host.  Results are bit-identical to the reference's functions of the same names
 // (homo/fhe_resize.h:143-392, homo/fhe_decode.h:48-242, homo/server_decode.cpp:120-137) called one ciphertext at a

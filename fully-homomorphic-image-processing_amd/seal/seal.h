@@ -1210,6 +1210,33 @@ inline void ring_mul(const CtxState &s, const DevBuf &a, size_t a_polys, const D
         check(fhe_dyadic_multiply(s.h, out.ptr() + p * s.poly_words(), b_ntt.ptr(), out.ptr() + p * s.poly_words(), 1, nullptr), "dyadic");
     check(fhe_ntt_inverse(s.h, out.ptr(), out.ptr(), a_polys, nullptr), "intt");
 }
+// one key-switching key [k][digits][2][k][n], written in COEFFICIENT form at dst (device), for the target polynomial `target` (host, [k][n]
+// coefficient form): entry (i, d) = (-(a s + e) + 2^(dbc d) target on RNS component i only, a).  make_evk: target = s^j; Galois keys: sigma_g(s).
+inline void make_switch_key(const CtxState &s, Sampler &smp, const std::vector<uint64_t> &target, const DevBuf &sk_ntt, int decomposition_bit_count, uint32_t nd,
+                            uint64_t *dst_key) {
+    const size_t pw = s.poly_words();
+    for (uint32_t i = 0; i < s.k; ++i)
+        for (uint32_t d = 0; d < nd; ++d) {
+            std::vector<uint64_t> a = smp.uniform(), e = smp.noise();
+            DevBuf da(pw), de(pw), as;
+            da.upload(a.data(), pw);
+            de.upload(e.data(), pw);
+            ring_mul(s, da, 1, sk_ntt, as);
+            check(fhe_add(s.h, as.ptr(), de.ptr(), as.ptr(), 1, nullptr), "add");
+            check(fhe_negate(s.h, as.ptr(), as.ptr(), 1, nullptr), "negate");
+            std::vector<uint64_t> k0(pw);
+            as.download(k0.data(), pw);
+            const uint64_t qi = s.q[i], wd = powmod(2, (uint64_t)decomposition_bit_count * d, qi);
+            for (uint32_t c = 0; c < s.n; ++c) {        // + w^d target in RNS component i only
+                uint64_t &x = k0[(size_t)i * s.n + c];
+                x = (uint64_t)(((u128)x + mulmod(target[(size_t)i * s.n + c], wd, qi)) % qi);
+            }
+            uint64_t *dst = dst_key + (((size_t)i * nd + d) * 2) * pw;
+            check(fhe_upload(dst, k0.data(), pw * 8, nullptr), "upload");
+            check(fhe_upload(dst + pw, a.data(), pw * 8, nullptr), "upload");
+            check(fhe_stream_sync(nullptr), "sync");
+        }
+}
 // evaluation keys for s^2 (SEAL 2.3 generate_evaluation_keys(dbc, keys)): evk[i][d] = (-(a s + e) + 2^(dbc d) s^2 E_i, a),
 // [k][digits][2][k][n], NTT form.  sk: [k][n] coefficient form, sk_ntt its transform.
 // count > 1 (generate_evaluation_keys(dbc, count, keys)): the keys for s^2 .. s^(count+1) one after the other, [count][k][digits][2][k][n]
@@ -1228,27 +1255,7 @@ inline void make_evk(const CtxState &s, const DevBuf &sk, const DevBuf &sk_ntt, 
     else { ring_mul(s, s2, 1, sk_ntt, nxt); check(fhe_copy(s2.ptr(), nxt.ptr(), pw * 8, nullptr), "copy"); check(fhe_stream_sync(nullptr), "sync"); }
     std::vector<uint64_t> hs2(pw);
     s2.download(hs2.data(), pw);
-    for (uint32_t i = 0; i < s.k; ++i)
-        for (uint32_t d = 0; d < nd; ++d) {
-            std::vector<uint64_t> a = smp.uniform(), e = smp.noise();
-            DevBuf da(pw), de(pw), as;
-            da.upload(a.data(), pw);
-            de.upload(e.data(), pw);
-            ring_mul(s, da, 1, sk_ntt, as);
-            check(fhe_add(s.h, as.ptr(), de.ptr(), as.ptr(), 1, nullptr), "add");
-            check(fhe_negate(s.h, as.ptr(), as.ptr(), 1, nullptr), "negate");
-            std::vector<uint64_t> k0(pw);
-            as.download(k0.data(), pw);
-            const uint64_t qi = s.q[i], wd = powmod(2, (uint64_t)decomposition_bit_count * d, qi);
-            for (uint32_t c = 0; c < s.n; ++c) {        // + w^d s^2 in RNS component i only
-                uint64_t &x = k0[(size_t)i * s.n + c];
-                x = (uint64_t)(((u128)x + mulmod(hs2[(size_t)i * s.n + c], wd, qi)) % qi);
-            }
-            uint64_t *dst = out.ptr() + (size_t)j * set_words + (((size_t)i * nd + d) * 2) * pw;
-            check(fhe_upload(dst, k0.data(), pw * 8, nullptr), "upload");
-            check(fhe_upload(dst + pw, a.data(), pw * 8, nullptr), "upload");
-            check(fhe_stream_sync(nullptr), "sync");
-        }
+    make_switch_key(s, smp, hs2, sk_ntt, decomposition_bit_count, nd, out.ptr() + (size_t)j * set_words);
     }
     check(fhe_ntt_forward(s.h, out.ptr(), out.ptr(), (uint64_t)count * s.k * nd * 2, nullptr), "ntt");
     check(fhe_stream_sync(nullptr), "sync");
@@ -1771,6 +1778,157 @@ inline std::vector<Ciphertext> resize_plain(const SEALContext &ctx, const std::v
     detail::check(fhe_stream_sync(nullptr), "sync");
     return res;
 }
+// ---- batched plaintext slots and Galois rotations (include/fhe_hip.h: seal::PolyCRTBuilder, seal::GaloisKeys, Evaluator::rotate_rows /
+// rotate_columns of SEAL 2.3) as batch helpers; they are not nodes of the lazy Evaluator graph -------------------------------------------
+// PolyCRTBuilder::compose / decompose: n slot values below t (row 0, then row 1) <-> the plaintext; t must be prime, t = 1 (mod 2n)
+inline Plaintext batch_encode(const SEALContext &ctx, const std::vector<uint64_t> &slots) {
+    const detail::CtxState &s = *ctx.state();
+    if (slots.size() != s.n) throw std::invalid_argument("batch_encode needs n slot values");
+    std::vector<uint64_t> c(s.n);
+    detail::check(fhe_batch_encode(s.n, ctx.plain_modulus().value(), slots.data(), 1, c.data()), "batch_encode");
+    return Plaintext(std::move(c));
+}
+inline std::vector<uint64_t> batch_decode(const SEALContext &ctx, const Plaintext &plain) {
+    const detail::CtxState &s = *ctx.state();
+    std::vector<uint64_t> c(plain.data()), out(s.n);
+    if (c.size() > s.n) throw std::invalid_argument("batch_decode: the plaintext has more than n coefficients");
+    c.resize(s.n, 0);
+    detail::check(fhe_batch_decode(s.n, ctx.plain_modulus().value(), c.data(), 1, out.data()), "batch_decode");
+    return out;
+}
+// Galois element -> key-switching key ([k][digits][2][k][n], NTT form, the library's slot order) and their decomposition bit count.
+// Stream record: magic "FHEHIPG\0", u32 dbc, digits, count, k, n, reserved; per key u32 element, u32 reserved, k * digits * 2 * k * n words.
+class GaloisKeys {
+public:
+    int decomposition_bit_count() const { return (int)dbc; }
+    bool has(uint32_t g) const { return keys.count(g) != 0; }
+    const uint64_t *key(uint32_t g) const {
+        auto it = keys.find(g);
+        if (it == keys.end()) throw std::invalid_argument("no Galois key for element " + std::to_string(g));
+        return it->second->ptr();
+    }
+    size_t key_words() const { return (size_t)k * digits * 2 * k * n; }
+    void require_for(const detail::CtxState &s, const char *who) const {
+        if (keys.empty() || k != s.k || n != s.n) throw std::invalid_argument(std::string(who) + ": the Galois keys are empty or belong to another context");
+        if (dbc < 1 || dbc > 60 || digits != fhe_evk_digits(s.h, dbc))
+            throw std::invalid_argument(std::string(who) + ": the Galois keys' digit count does not fit their decomposition bit count on this context");
+    }
+    void save(std::ostream &os) const {
+        const char magic[8] = {'F', 'H', 'E', 'H', 'I', 'P', 'G', 0};
+        const uint32_t hdr[6] = {dbc, digits, (uint32_t)keys.size(), k, n, 0};
+        os.write(magic, 8);
+        os.write((const char *)hdr, sizeof hdr);
+        std::vector<uint64_t> h(key_words());
+        for (const auto &kv : keys) {
+            const uint32_t rec[2] = {kv.first, 0};
+            os.write((const char *)rec, sizeof rec);
+            kv.second->download(h.data(), h.size());
+            os.write((const char *)h.data(), (std::streamsize)(h.size() * 8));
+        }
+    }
+    void load(std::istream &is) {
+        char magic[8];
+        uint32_t hdr[6];
+        is.read(magic, 8);
+        is.read((char *)hdr, sizeof hdr);
+        if (!is || std::memcmp(magic, "FHEHIPG", 8) != 0) throw std::invalid_argument("stream does not hold Galois keys");
+        if (hdr[0] < 1 || hdr[0] > 60 || hdr[1] < 1 || hdr[1] > 61 || hdr[2] < 1 || hdr[2] > 64 || hdr[3] < 1 || hdr[3] > FHE_MAX_K || hdr[4] < 1024 ||
+            hdr[4] > 16384 || (hdr[4] & (hdr[4] - 1)))
+            throw std::invalid_argument("Galois key header out of range");
+        GaloisKeys fresh;
+        fresh.dbc = hdr[0]; fresh.digits = hdr[1]; fresh.k = hdr[3]; fresh.n = hdr[4];
+        std::vector<uint64_t> h(fresh.key_words());
+        for (uint32_t i = 0; i < hdr[2]; ++i) {
+            uint32_t rec[2];
+            is.read((char *)rec, sizeof rec);
+            is.read((char *)h.data(), (std::streamsize)(h.size() * 8));
+            if (!is) throw std::invalid_argument("truncated Galois key stream");
+            if (!(rec[0] & 1) || rec[0] == 1 || rec[0] >= 2 * fresh.n) throw std::invalid_argument("Galois element out of range");
+            std::shared_ptr<detail::DevBuf> b = std::make_shared<detail::DevBuf>(h.size());
+            b->upload(h.data(), h.size());
+            fresh.keys[rec[0]] = std::move(b);
+        }
+        *this = std::move(fresh);
+    }
+    std::map<uint32_t, std::shared_ptr<detail::DevBuf>> keys;
+    uint32_t dbc = 0, digits = 0, k = 0, n = 0;
+};
+inline uint32_t galois_element(const SEALContext &ctx, int steps, bool swap_rows = false) {
+    uint32_t g = 0;
+    detail::check(fhe_galois_element(ctx.state()->n, steps, swap_rows ? 1 : 0, &g), "galois_element");
+    return g;
+}
+// KeyGenerator::generate_galois_keys of SEAL 2.3 from the secret key: one key per element for the target sigma_g(s); an empty list gives
+// the default set {3^(+-2^i) mod 2n : 0 <= i < log2(n/2)} and 2n - 1
+inline void generate_galois_keys(const SEALContext &ctx, const SecretKey &sk, int decomposition_bit_count, std::vector<uint32_t> elements, GaloisKeys &out) {
+    const detail::CtxState &s = *ctx.state();
+    if (decomposition_bit_count < 1 || decomposition_bit_count > 60) throw std::invalid_argument("decomposition_bit_count");
+    if (sk.buf.words() != s.poly_words()) throw std::invalid_argument("secret key does not match the context");
+    if (elements.empty()) {
+        for (uint32_t i = 0; (1u << i) < s.n / 2; ++i) {
+            elements.push_back(galois_element(ctx, (int)(1u << i)));
+            elements.push_back(galois_element(ctx, -(int)(1u << i)));
+        }
+        elements.push_back(2 * s.n - 1);
+    }
+    const size_t pw = s.poly_words();
+    detail::DevBuf sk_ntt(pw);
+    detail::check(fhe_ntt_forward(s.h, sk.buf.ptr(), sk_ntt.ptr(), 1, nullptr), "ntt");
+    std::vector<uint64_t> hs(pw), target(pw);
+    sk.buf.download(hs.data(), pw);
+    detail::Sampler smp(s);
+    GaloisKeys fresh;
+    fresh.dbc = (uint32_t)decomposition_bit_count; fresh.digits = fhe_evk_digits(s.h, fresh.dbc); fresh.k = s.k; fresh.n = s.n;
+    for (uint32_t g : elements) {
+        if (!(g & 1) || g == 1 || g >= 2 * s.n) throw std::invalid_argument("Galois element must be odd and in (1, 2n)");
+        if (fresh.keys.count(g)) continue;
+        for (uint32_t i = 0; i < s.k; ++i)                               // sigma_g(s): coefficient c goes to c g mod 2n, negated past n
+            for (uint32_t c = 0; c < s.n; ++c) {
+                const uint64_t e = (uint64_t)c * g % (2 * (uint64_t)s.n), v = hs[(size_t)i * s.n + c];
+                target[(size_t)i * s.n + (e % s.n)] = e < s.n ? v : (v ? s.q[i] - v : 0);
+            }
+        std::shared_ptr<detail::DevBuf> b = std::make_shared<detail::DevBuf>(fresh.key_words());
+        detail::make_switch_key(s, smp, target, sk_ntt, decomposition_bit_count, fresh.digits, b->ptr());
+        detail::check(fhe_ntt_forward(s.h, b->ptr(), b->ptr(), (uint64_t)s.k * fresh.digits * 2, nullptr), "ntt");
+        detail::check(fhe_stream_sync(nullptr), "sync");
+        fresh.keys[g] = std::move(b);
+    }
+    out = std::move(fresh);
+}
+// Evaluator::apply_galois on a batch of size-2 ciphertexts, in place (fhe_apply_galois: one call for the whole batch)
+inline void apply_galois(const SEALContext &ctx, std::vector<Ciphertext> &cts, uint32_t g, const GaloisKeys &keys) {
+    const detail::CtxState &s = *ctx.state();
+    keys.require_for(s, "apply_galois");
+    const uint64_t *key = keys.key(g);
+    if (cts.empty()) return;
+    const size_t ctw = 2 * s.poly_words();
+    detail::DevBuf buf(cts.size() * ctw);
+    for (size_t i = 0; i < cts.size(); ++i) {
+        if (cts[i].size() != 2 || cts[i].k() != s.k || cts[i].n() != s.n) throw std::invalid_argument("apply_galois needs size-2 ciphertexts of this context (relinearize first)");
+        detail::check(fhe_copy(buf.ptr() + i * ctw, static_cast<const Ciphertext &>(cts[i]).ptr(), ctw * 8, nullptr), "copy");
+    }
+    const size_t bytes = fhe_apply_galois_scratch_bytes(s.h, keys.dbc, cts.size());
+    detail::DevBuf scratch((bytes + 7) / 8 + 1);
+    detail::check(fhe_apply_galois(s.h, buf.ptr(), ctw, buf.ptr(), ctw, cts.size(), g, key, keys.dbc, scratch.ptr(), bytes, nullptr), "apply_galois");
+    for (size_t i = 0; i < cts.size(); ++i) detail::check(fhe_copy(cts[i].ptr(), buf.ptr() + i * ctw, ctw * 8, nullptr), "copy");
+    detail::check(fhe_stream_sync(nullptr), "sync");
+}
+// Evaluator::rotate_rows: both rows of slots LEFT by `steps` (negative: right).  Steps are reduced into (-n/4, n/4]; one apply_galois if
+// the keys hold 3^steps mod 2n, otherwise the hops 3^(+-2^i) for the set bits i of |steps| in ascending order; steps == 0 leaves the batch as it is
+inline void rotate_rows(const SEALContext &ctx, std::vector<Ciphertext> &cts, int steps, const GaloisKeys &keys) {
+    const int half = (int)(ctx.state()->n / 2);
+    int r = steps % half;
+    if (r < 0) r += half;
+    if (r > half / 2) r -= half;
+    if (r == 0) return;
+    const uint32_t g = galois_element(ctx, r);
+    if (keys.has(g)) { apply_galois(ctx, cts, g, keys); return; }
+    const int sign = r > 0 ? 1 : -1, mag = r > 0 ? r : -r;
+    for (int i = 0; (1 << i) <= mag; ++i)
+        if ((mag >> i) & 1) apply_galois(ctx, cts, galois_element(ctx, sign * (1 << i)), keys);
+}
+// Evaluator::rotate_columns: the two rows of slots swapped (g = 2n - 1)
+inline void rotate_columns(const SEALContext &ctx, std::vector<Ciphertext> &cts, const GaloisKeys &keys) { apply_galois(ctx, cts, 2 * ctx.state()->n - 1, keys); }
 }  // namespace hip
 
 }  // namespace seal

@@ -80,7 +80,8 @@ const char *fhe_last_error(void);
  *      relinearises); fhe_relinearize_to rejects partially overlapping input / output ranges.  Version 4 also carries
  *      fhe_idct_plan_create / destroy, fhe_idct8x8_scratch_bytes, fhe_idct8x8_dequant and fhe_ycc_to_rgb_blocks, added later:
  *      new entry points only, no existing signature or contract changed.  The same holds for the fhe_filter_* entry points (2-D convolution)
- *      and for fhe_weight_table_*, fhe_remap* and fhe_resample_axis_plan (resampling with public weights).
+ *      and for fhe_weight_table_*, fhe_remap* and fhe_resample_axis_plan (resampling with public weights), and for fhe_batch_encode /
+ *      fhe_batch_decode, fhe_galois_element and fhe_apply_galois (batched slots and Galois rotations).
  * A host compiled against this header compares fhe_abi_version() with FHE_ABI_VERSION before anything else (the Python
  * binding and seal/seal.h do). */
 #define FHE_ABI_VERSION 4
@@ -283,6 +284,39 @@ size_t fhe_relinearize_n_scratch_bytes(const fhe_ctx *ctx, uint32_t size, uint32
 int fhe_relinearize_n(const fhe_ctx *ctx, uint64_t *ct, uint32_t size, uint64_t ct_stride_words, uint64_t *out2,
                       uint64_t out_stride_words, uint64_t count, const uint64_t *d_evk_ntt, uint32_t dbc, void *scratch,
                       size_t scratch_bytes, fhe_stream stream);
+
+/* ---- batched plaintext slots and Galois rotations: seal::PolyCRTBuilder, seal::GaloisKeys, seal::Evaluator::rotate_rows /
+ * rotate_columns (SEAL 2.3; the reference never calls them: every pixel of its streams is one ciphertext).  New entry points only.
+ *
+ * Slots.  For a PRIME plain modulus t = 1 (mod 2n) the plaintext ring splits into n slots: with zeta the SMALLEST primitive 2n-th root
+ * of unity modulo t, slot (r, j), r in {0, 1}, 0 <= j < n/2, of a plaintext m is m(zeta^e) mod t, e = 3^j mod 2n for row 0 and
+ * e = 2n - 3^j mod 2n for row 1; the flat slot order is row 0, then row 1.  add / sub / multiply_plain / multiply / square act slot by slot.
+ * fhe_batch_encode writes the `count` plaintexts (n coefficients below t each) whose slots are the given values, fhe_batch_decode
+ * evaluates them: an inverse and a forward number-theoretic transform modulo t on the host, no device.  FHE_ERR_PARAM for a t that is
+ * not prime or not 1 mod 2n (the presets' 2^14 is refused), a t of more than 60 bits, and a value >= t. */
+int fhe_batch_encode(uint32_t n, uint64_t t, const uint64_t *slots, uint64_t count, uint64_t *plain);
+int fhe_batch_decode(uint32_t n, uint64_t t, const uint64_t *plain, uint64_t count, uint64_t *slots);
+/* Automorphism.  For odd g in (1, 2n), sigma_g maps x^i to x^(i g mod 2n) with x^n = -1: coefficient i of the input goes to position
+ * e = i g mod 2n if e < n, otherwise to position e - n NEGATED modulo q_i (the negation of 0 is 0, not q_i).  On the slots above
+ * sigma_g with g = 3^s mod 2n rotates both rows LEFT by s (slot (r, j) of the result is slot (r, j + s mod n/2) of the input) and
+ * g = 2n - 1 swaps the rows.  fhe_galois_element (host only) gives g = 3^steps mod 2n -- the inverse power for negative steps; steps
+ * count modulo n/2 --, times 2n - 1 if swap_rows != 0; steps == 0 without the swap gives 1, the identity, which fhe_apply_galois refuses. */
+int fhe_galois_element(uint32_t n, int steps, int swap_rows, uint32_t *g);
+/* apply_galois(ct, g, key_g) for `count` ciphertexts of size 2 (other sizes are refused by the hosts, as SEAL 2.3 does):
+ *     out = relinearize-step([sigma_g(c0), 0, sigma_g(c1)])
+ * i.e. the digits of sigma_g(c1)'s residues (dbc bits each, per source prime: exactly fhe_relinearize_poly's rule with src_poly = 2)
+ * are multiplied with key_g and added to (sigma_g(c0), 0).  d_key_ntt: [k][digits][2][k][n] in NTT form, fhe_evk_words(ctx, dbc) words,
+ * made like the evaluation key for s^2 but for the target sigma_g(s): entry (i, d) = (-(a s + e) + 2^(dbc d) sigma_g(s) on component i
+ * only, a).  ct2 [c * ct_stride_words ...] -> out2[c * out_stride_words ...]; aliasing rule of fhe_relinearize_to: out2 IS the input
+ * (same pointer, same stride) or does not overlap it.  Bit-identical to that composition on every context (csrc/galois.hip: the
+ * kernels read their source polynomials through the automorphism; FHE_GALOIS_STAGED=1 at fhe_ctx_create materialises
+ * [sigma(c0), 0, sigma(c1)] in scratch and runs fhe_relinearize_poly on it).  Everything is checked before anything is enqueued: g even,
+ * g == 1, g >= 2n, strides below 2 k n, short scratch, a forbidden overlap of input, output and scratch: FHE_ERR_PARAM.  count == 0 is
+ * a no-op. */
+size_t fhe_apply_galois_scratch_bytes(const fhe_ctx *ctx, uint32_t dbc, uint64_t count);
+int fhe_apply_galois(const fhe_ctx *ctx, const uint64_t *ct2, uint64_t ct_stride_words, uint64_t *out2, uint64_t out_stride_words,
+                     uint64_t count, uint32_t galois_elt, const uint64_t *d_key_ntt, uint32_t dbc, void *scratch, size_t scratch_bytes,
+                     fhe_stream stream);
 
 /* ---- fused block circuit: encrypted_dct (homo/fhe_image.h:196-288) followed by quantize_fhe
  * (homo/fhe_image.h:294-305) on n_blocks independent 8x8 blocks.  in/out: [n_blocks][64][2][k][n].
