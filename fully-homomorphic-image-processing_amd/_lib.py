@@ -87,6 +87,11 @@ SIGNATURES = {
     "fhe_galois_element": (_i, [_u32, _i, _i, C.POINTER(_u32)]),
     "fhe_apply_galois_scratch_bytes": (_sz, [_vp, _u32, _u64]),
     "fhe_apply_galois": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u32, _vp, _u32, _vp, _sz, _vp]),
+    "fhe_block8x8_plan_create": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "fhe_block8x8_plan_destroy": (_i, [_vp]),
+    "fhe_block8x8_scalar": (_i, [_vp, _vp, _vp, _vp, _u32, _u64, _vp]),
+    "fhe_channel_mix": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, _u64, _u64, _vp, _u64, _u64, _u32, _u64, _vp]),
+    "fhe_dct8_matrix": (_i, [_i, _vp]),
     "fhe_dct_plan_create": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(_vp)]),
     "fhe_dct_plan_destroy": (_i, [_vp]),
     "fhe_dct8x8_scratch_bytes": (_sz, [_vp, _u64]),

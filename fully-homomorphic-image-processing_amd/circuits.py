@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .evaluator import FractionalEncoder, PreparedPlain, _ptr, _stream, check_evaluation_keys
+from .evaluator import YQT, Block8x8Plan, FractionalEncoder, PreparedPlain, _ptr, _stream, check_evaluation_keys
 
 
 class PlainCache:
@@ -608,3 +608,95 @@ def packed_filter2d(ev, keys, ct, tile_w, weights_int, kw, kh, anchor=None):
     if acc is None:
         raise ValueError("packed_filter2d: every weight is zero modulo t")
     return acc
+
+
+# ---- packed JPEG: 8x8 blocks packed by POSITION (client.pack_blocks), the transform as integer maps across ciphertexts ----------------
+# A fixed-point transform of its own: its ciphertexts and decrypted values are NOT those of fhe_dct8x8_quant / dct8x8_quant, which follow
+# the reference's FractionalEncoder circuit.  Values carry `scale_bits` fractional bits; client.descale rounds them away after decryption.
+def dct8_matrix(bits=8):
+    """[8][8] int64: D[u][x] = round-half-away(2^bits c_u / 2 cos((2 x + 1) u pi / 16)) (fhe_dct8_matrix, host only)"""
+    D = np.zeros(64, dtype=np.int64)
+    _lib.call("fhe_dct8_matrix", int(bits), D.ctypes.data_as(C.c_void_p))
+    return D.reshape(8, 8)
+
+
+class PackedBlockPlan:
+    """The integer map Y = post * (L (pre * X) R^T) of one 8x8 block position-packed over 64 ciphertexts, with its fixed-point scale.
+    ctx None: the integers alone (model, bound), no device plan."""
+
+    def __init__(self, ctx, L, R, pre, post, scale_bits):
+        self.L, self.R = np.asarray(L, dtype=np.int64).reshape(8, 8), np.asarray(R, dtype=np.int64).reshape(8, 8)
+        self.pre = None if pre is None else np.asarray(pre, dtype=np.int64).reshape(8, 8)
+        self.post = None if post is None else np.asarray(post, dtype=np.int64).reshape(8, 8)
+        self.scale_bits = int(scale_bits)
+        self.ctx = ctx
+        self.plan = None if ctx is None else Block8x8Plan(ctx, self.L, self.R, self.pre, self.post)
+
+    def model(self, x):
+        """the exact integer map on [..., 8, 8] values (Python integers: no overflow)"""
+        x = np.asarray(x).astype(object)
+        if self.pre is not None:
+            x = x * self.pre.astype(object)
+        y = np.matmul(np.matmul(self.L.astype(object), x), self.R.astype(object).T)
+        return y if self.post is None else y * self.post.astype(object)
+
+    def bound(self, input_bound):
+        """the exact worst-case |slot value| of any output for inputs of magnitude at most input_bound (a number, or [8][8] per position):
+        max over (u, v) of |post[u][v]| sum_x,y |L[u][x]| |R[v][y]| |pre[x][y]| bound[x][y]; the client picks t > 2 * bound"""
+        b = np.broadcast_to(np.asarray(input_bound, dtype=object), (8, 8)) * (1 if self.pre is None else np.abs(self.pre).astype(object))
+        y = np.matmul(np.matmul(np.abs(self.L).astype(object), b), np.abs(self.R).astype(object).T)
+        if self.post is not None:
+            y = y * np.abs(self.post).astype(object)
+        return int(y.max())
+
+
+def _quant8(quant):
+    q = np.asarray(quant, dtype=np.int64).reshape(-1)
+    if q.size != 64 or (q <= 0).any():
+        raise ValueError("a quantisation table has 64 positive integers")
+    return q.reshape(8, 8)
+
+
+def packed_dct_plan(ctx, quant=YQT, dct_bits=8, quant_bits=8):
+    """forward 8x8 DCT and quantisation: L = R = D(dct_bits), post[u][v] = round(2^quant_bits / Q[u][v]) = (2^(quant_bits + 1) + Q) // (2 Q);
+    the slots hold quantised coefficients times 2^(2 dct_bits + quant_bits)"""
+    Q = _quant8(quant)
+    D = dct8_matrix(dct_bits)
+    post = ((1 << (quant_bits + 1)) + Q) // (2 * Q)
+    return PackedBlockPlan(ctx, D, D, None, post, 2 * dct_bits + quant_bits)
+
+
+def packed_idct_plan(ctx, quant=YQT, dct_bits=8):
+    """dequantisation (pre = Q: exact) and the inverse 8x8 DCT: L = R = D(dct_bits)^T; the slots hold pixels times 2^(2 dct_bits)"""
+    D = dct8_matrix(dct_bits)
+    return PackedBlockPlan(ctx, D.T, D.T, _quant8(quant), None, 2 * dct_bits)
+
+
+def _round_half_away(v):
+    return int(math.floor(abs(v) + 0.5)) * (1 if v >= 0 else -1)
+
+
+def packed_rgb_to_ycc(bits=8):
+    """[3][3] int64: the JFIF RGB -> YCbCr matrix in `bits` fractional bits, each entry rounded half away from zero"""
+    m = [[0.299, 0.587, 0.114], [-0.168736, -0.331264, 0.5], [0.5, -0.418688, -0.081312]]
+    return np.array([[_round_half_away(v * (1 << bits)) for v in row] for row in m], dtype=np.int64)
+
+
+def packed_ycc_to_rgb(bits=8):
+    """[3][3] int64: the JFIF YCbCr -> RGB matrix in `bits` fractional bits, each entry rounded half away from zero"""
+    m = [[1.0, 0.0, 1.402], [1.0, -0.344136, -0.714136], [1.0, 1.772, 0.0]]
+    return np.array([[_round_half_away(v * (1 << bits)) for v in row] for row in m], dtype=np.int64)
+
+
+def packed_jpeg_compress(ev, plan, r, g, b, colour_bits=8):
+    """position-packed R, G, B groups ([groups, 64, size, k, n] each, pixel values 0 .. 255 in the slots) -> [3, groups, 64, size, k, n]:
+    the colour mix M = packed_rgb_to_ycc(colour_bits) with the level shift as its bias (Y - 128; the +128 of Cb, Cr and the shift cancel),
+    then the block plan per channel (`plan`: one PackedBlockPlan, or three for Y, Cb, Cr).  The slots hold quantised coefficients
+    times 2^(plan.scale_bits + colour_bits)."""
+    planes = torch.stack([r, g, b]).contiguous()
+    ev.channel_mix(packed_rgb_to_ycc(colour_bits), planes, bias=[-(128 << colour_bits), 0, 0], out=planes)
+    if isinstance(plan, PackedBlockPlan):
+        return ev.block8x8_scalar(plan.plan, planes, out=planes)
+    for ch, p in enumerate(plan):
+        ev.block8x8_scalar(p.plan, planes[ch], out=planes[ch])
+    return planes

@@ -365,3 +365,37 @@ class BatchEncoder:
             plains = plains.detach().cpu().contiguous().numpy().view(np.uint64)
         a = np.asarray(plains)
         return self._run("fhe_batch_decode", a[None])[0] if a.ndim == 1 else self._run("fhe_batch_decode", a)
+
+
+# ---- position-packed 8x8 blocks (include/fhe_hip.h "integer linear maps across slot-packed ciphertexts"; circuits.packed_dct_plan) ----
+def pack_blocks(channel, width, height, n, t=None):
+    """[groups][64][n] slot values: block b of `channel` (raster order, as blocks_of) goes to group b // n, slot b % n; position 8 r + c of
+    the block names the ciphertext of the group; unused slots are 0.  int64, or uint64 reduced modulo t when t is given (what
+    BatchEncoder.encode takes)."""
+    blocks = blocks_of(np.asarray(channel).astype(np.int64), width, height)
+    groups = max(1, (len(blocks) + n - 1) // n)
+    out = np.zeros((groups, 64, n), dtype=np.int64)
+    for b, blk in enumerate(blocks):
+        out[b // n, :, b % n] = blk
+    return out if t is None else (out % np.int64(t)).astype(np.uint64)
+
+
+def unpack_blocks(slots, width, height):
+    """the inverse of pack_blocks: [groups][64][n] values -> [height - height % 8][width - width % 8]"""
+    a = np.asarray(slots)
+    bw, bh = width // 8, height // 8
+    n = a.shape[-1]
+    out = np.zeros((bh * 8, bw * 8), dtype=a.dtype)
+    for b in range(bw * bh):
+        j, i = divmod(b, bw)
+        out[8 * j:8 * j + 8, 8 * i:8 * i + 8] = a[b // n, :, b % n].reshape(8, 8)
+    return out
+
+
+def descale(values, scale_bits, t):
+    """slot values modulo t -> integers: centred modulo t, divided by 2^scale_bits, rounded half away from zero (int64 for t < 2^63)"""
+    v = np.asarray(values).astype(object) % int(t)
+    v = np.where(v > (int(t) - 1) // 2, v - int(t), v)
+    half = (1 << scale_bits) >> 1
+    mag = (np.abs(v) + half) >> scale_bits if scale_bits else np.abs(v)
+    return (np.where(v < 0, -mag, mag)).astype(np.int64)

@@ -318,6 +318,38 @@ class WeightTable:
             self.h = None
 
 
+class Block8x8Plan:
+    """Constants of fhe_block8x8_scalar (include/fhe_hip.h "integer linear maps across slot-packed ciphertexts"): integer 8x8 matrices L
+    (down the columns) and R (along the rows), optional per-input scalars `pre` and per-output scalars `post` ([8][8] or [64], row-major;
+    None = all ones).  Every scalar w must satisfy |w| <= min((t - 1) / 2, 2^31 - 1)."""
+
+    def __init__(self, ctx, L, R, pre=None, post=None):
+        def arr(a, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a, dtype=np.int64).reshape(-1))
+            if a.size != 64:
+                raise ValueError("Block8x8Plan: %s must hold 64 integers, got %d" % (name, a.size))
+            return a
+        self.ctx = ctx
+        self.L, self.R, self.pre, self.post = arr(L, "L"), arr(R, "R"), arr(pre, "pre"), arr(post, "post")
+        if self.L is None or self.R is None:
+            raise ValueError("Block8x8Plan: L and R are required")
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        h = C.c_void_p()
+        _lib.call("fhe_block8x8_plan_create", ctx.h, vp(self.L), vp(self.R), vp(self.pre), vp(self.post), _stream(), C.byref(h))
+        self.h = h
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h:
+            try:
+                _lib.load().fhe_block8x8_plan_destroy(h)
+            except Exception:
+                pass
+            self.h = None
+
+
 def check_evaluation_keys(ctx, evk_ntt, dbc, need, who):
     """The library takes the keys as a bare pointer and reads need * fhe_evk_words(ctx, dbc) words behind it (include/fhe_hip.h): the host
     checks that the tensor it hands over holds them -- a key tensor made for another decomposition bit count (fewer digits), another context or
@@ -581,6 +613,54 @@ class Evaluator:
     def rotate_columns(self, a, keys, out=None):
         """the two rows of slots swapped (g = 2n - 1)"""
         return self.apply_galois(a, 2 * self.ctx.n - 1, keys, out=out)
+
+    # -- integer linear maps across slot-packed ciphertexts (include/fhe_hip.h; csrc/packed.hip) ------------------------------------
+    def block8x8_scalar(self, plan, blocks, out=None):
+        """Y[u][v] = post[u][v] sum_x,y L[u][x] R[v][y] pre[x][y] X[x][y] on groups of 64 ciphertexts, [..., 64, size, k, n] (ciphertext
+        8 x + y of a group is X[x][y]), bit for bit the multiply_plain / add composition; one kernel.  `out` may be `blocks` itself."""
+        kn = (self.ctx.k, self.ctx.n)
+        if not (isinstance(blocks, torch.Tensor) and blocks.dim() >= 4 and tuple(blocks.shape[-2:]) == kn and blocks.shape[-4] == 64 and blocks.dtype == torch.int64
+                and blocks.is_contiguous() and blocks.device == self.ctx.device):
+            raise ValueError("block8x8_scalar: `blocks` must be a contiguous int64 tensor [..., 64, size, k, n] = [..., 64, size, %d, %d] on the context's "
+                             "device, got %r" % (kn + (tuple(getattr(blocks, "shape", ())),)))
+        if plan.ctx is not self.ctx:
+            raise ValueError("block8x8_scalar: the plan was built for another context")
+        if out is not None and (tuple(out.shape) != tuple(blocks.shape) or out.dtype != blocks.dtype or not out.is_contiguous() or out.device != blocks.device):
+            raise ValueError("block8x8_scalar: `out` must be a contiguous tensor like `blocks` (%r), got %r" % (tuple(blocks.shape), tuple(out.shape)))
+        out = torch.empty_like(blocks) if out is None else out
+        size = int(blocks.shape[-3])
+        count = blocks.numel() // (64 * size * kn[0] * kn[1])
+        _lib.call("fhe_block8x8_scalar", self.ctx.h, plan.h, _ptr(blocks), _ptr(out), size, count, _stream())
+        return out
+
+    def channel_mix(self, M, planes, bias=None, out=None):
+        """out_i = sum_j M[i][j] planes_j (+ add_plain of [bias_i mod t]) on planar batches: planes [c, ..., size, k, n], M integers [m][c],
+        returns [m, ..., size, k, n]; one kernel (fhe_channel_mix).  `out` may be `planes` itself when m == c."""
+        kn = (self.ctx.k, self.ctx.n)
+        Mx = np.asarray(M, dtype=np.int64)
+        if Mx.ndim != 2 or not (1 <= Mx.shape[0] <= 8 and 1 <= Mx.shape[1] <= 8):
+            raise ValueError("channel_mix: M must be an integer matrix [m][c] with 1 <= m, c <= 8, got shape %r" % (Mx.shape,))
+        m, c = int(Mx.shape[0]), int(Mx.shape[1])
+        if not (isinstance(planes, torch.Tensor) and planes.dim() >= 4 and tuple(planes.shape[-2:]) == kn and planes.shape[0] == c and planes.dtype == torch.int64
+                and planes.is_contiguous() and planes.device == self.ctx.device):
+            raise ValueError("channel_mix: `planes` must be a contiguous int64 tensor [c = %d, ..., size, k, n] on the context's device, got %r"
+                             % (c, tuple(getattr(planes, "shape", ()))))
+        shape = (m,) + tuple(planes.shape[1:])
+        if out is not None and (tuple(out.shape) != shape or out.dtype != planes.dtype or not out.is_contiguous() or out.device != planes.device):
+            raise ValueError("channel_mix: `out` must be a contiguous int64 tensor %r on the input's device, got %r" % (shape, tuple(out.shape)))
+        bv = None
+        if bias is not None:
+            bv = np.ascontiguousarray(np.asarray(bias, dtype=np.int64).reshape(-1))
+            if bv.size != m:
+                raise ValueError("channel_mix: %d biases for %d outputs" % (bv.size, m))
+        out = torch.empty(shape, dtype=torch.int64, device=planes.device) if out is None else out
+        size = int(planes.shape[-3])
+        ctw = size * kn[0] * kn[1]
+        count = planes.numel() // (c * ctw)
+        Mx = np.ascontiguousarray(Mx)
+        _lib.call("fhe_channel_mix", self.ctx.h, Mx.ctypes.data_as(C.c_void_p), None if bv is None else bv.ctypes.data_as(C.c_void_p), c, m,
+                  _ptr(planes), ctw, count * ctw, _ptr(out), ctw, count * ctw, size, count, _stream())
+        return out
 
     # -- primitives named by the north star ---------------------------------------------------------
     def cubic_coeffs(self, A, B, C, D):

@@ -9,6 +9,8 @@
 //   seal::hip::DeviceDecryptor   seal::Decryptor::decrypt (+ noise budgets) of a whole CiphertextBatch in one fhe_decrypt_batch
 //   seal::hip::Circuits          one fhe_circuits handle + scratch: cubic, linear, sample_bicubic, sample_linear,
 //                                resize_bicubic (shared offsets), homomorphic_sin / _cos, approximated_step, decode_channel
+//   seal::hip::Block8x8Plan,     integer linear maps across slot-packed ciphertexts on a CiphertextBatch (include/fhe_hip.h: the packed JPEG
+//   block8x8_scalar, channel_mix transform): groups of 64 ciphertexts packed by block position, planes of a colour conversion; dct8_matrix
 //
 // (The slot encoder and the Galois rotations -- seal::hip::batch_encode / batch_decode, GaloisKeys, generate_galois_keys, apply_galois,
 // rotate_rows, rotate_columns -- work on std::vector<seal::Ciphertext> and live in seal/seal.h, beside filter2d and remap.)
@@ -38,6 +40,8 @@ public:
     size_t count() const { return count_; }
     uint32_t size() const { return size_; }
     size_t ct_words() const { return (size_t)size_ * k_ * n_; }
+    // shaped for this context's k and n (an empty batch belongs to any)
+    bool of(const SEALContext &ctx) const { return !count_ || (k_ == ctx.state()->k && n_ == ctx.state()->n); }
     // an EMPTY batch has no allocation, and the C ABI refuses null pointers before it looks at the count: it gets the address of a two-word
     // placeholder, so that count == 0 is the no-op include/fhe_hip.h defines (the Python host does the same, evaluator._ptr)
     uint64_t *ptr() { return buf_.ptr() ? buf_.ptr() : placeholder(); }
@@ -380,6 +384,55 @@ private:
     detail::DevBuf evk_;                // relinearised mode: this handle's copy of the evaluation keys (must outlive h_)
     detail::DevBuf scratch_;
 };
+
+// ---- integer linear maps across slot-packed ciphertexts (include/fhe_hip.h: fhe_block8x8_scalar, fhe_channel_mix, fhe_dct8_matrix) -------
+// what Evaluator.block8x8_scalar / channel_mix and circuits.dct8_matrix are to the Python host
+inline std::vector<int64_t> dct8_matrix(int bits) {
+    std::vector<int64_t> D(64);
+    detail::check(fhe_dct8_matrix(bits, D.data()), "dct8_matrix");
+    return D;
+}
+
+// the constants of one 8x8 map (L, R: 64 integers, row-major; pre / post: 64 integers or empty = all ones); belongs to its context
+class Block8x8Plan {
+public:
+    Block8x8Plan(const SEALContext &ctx, const std::vector<int64_t> &L, const std::vector<int64_t> &R, const std::vector<int64_t> &pre = std::vector<int64_t>(),
+                 const std::vector<int64_t> &post = std::vector<int64_t>())
+        : ctx_(ctx), h_(nullptr) {
+        if (L.size() != 64 || R.size() != 64 || (!pre.empty() && pre.size() != 64) || (!post.empty() && post.size() != 64))
+            throw std::invalid_argument("Block8x8Plan: L, R (and pre, post when given) hold 64 integers");
+        detail::check(fhe_block8x8_plan_create(ctx.state()->h, L.data(), R.data(), pre.empty() ? nullptr : pre.data(), post.empty() ? nullptr : post.data(), nullptr, &h_),
+                      "block8x8_plan_create");
+    }
+    ~Block8x8Plan() { if (h_) fhe_block8x8_plan_destroy(h_); }
+    Block8x8Plan(const Block8x8Plan &) = delete;
+    Block8x8Plan &operator=(const Block8x8Plan &) = delete;
+    const fhe_block8x8_plan *handle() const { return h_; }
+    const SEALContext &context() const { return ctx_; }
+private:
+    SEALContext ctx_;
+    fhe_block8x8_plan *h_;
+};
+
+// groups of 64 ciphertexts, in place: batch [groups * 64][size][k][n], ciphertext 8 x + y of a group is X[x][y]
+inline void block8x8_scalar(const Block8x8Plan &plan, CiphertextBatch &blocks) {
+    if (blocks.count() % 64) throw std::invalid_argument("block8x8_scalar: the batch must hold whole groups of 64 ciphertexts");
+    if (!blocks.of(plan.context())) throw std::invalid_argument("block8x8_scalar: the batch does not belong to the plan's context");
+    detail::check(fhe_block8x8_scalar(plan.context().state()->h, plan.handle(), blocks.ptr(), blocks.ptr(), blocks.size(), blocks.count() / 64, nullptr), "block8x8_scalar");
+}
+
+// planar batches: `planes` holds c planes of count / c ciphertexts each, M is [m][c] row-major, bias has m entries or none; returns the m output planes
+inline CiphertextBatch channel_mix(const SEALContext &ctx, const std::vector<int64_t> &M, uint32_t c, uint32_t m, const CiphertextBatch &planes,
+                                   const std::vector<int64_t> &bias = std::vector<int64_t>()) {
+    if (!c || !m || M.size() != (size_t)c * m || planes.count() % c || (!bias.empty() && bias.size() != m)) throw std::invalid_argument("channel_mix: M is [m][c], planes holds c planes");
+    if (!planes.of(ctx)) throw std::invalid_argument("channel_mix: the batch does not belong to this context");
+    const size_t per = planes.count() / c;
+    CiphertextBatch out(ctx, per * m, planes.size());
+    const uint64_t ctw = planes.ct_words();
+    detail::check(fhe_channel_mix(ctx.state()->h, M.data(), bias.empty() ? nullptr : bias.data(), c, m, planes.ptr(), ctw, per * ctw, out.ptr(), ctw, per * ctw, planes.size(),
+                                  per, nullptr), "channel_mix");
+    return out;
+}
 
 }  // namespace hip
 }  // namespace seal

@@ -81,7 +81,8 @@ const char *fhe_last_error(void);
  *      fhe_idct_plan_create / destroy, fhe_idct8x8_scratch_bytes, fhe_idct8x8_dequant and fhe_ycc_to_rgb_blocks, added later:
  *      new entry points only, no existing signature or contract changed.  The same holds for the fhe_filter_* entry points (2-D convolution)
  *      and for fhe_weight_table_*, fhe_remap* and fhe_resample_axis_plan (resampling with public weights), and for fhe_batch_encode /
- *      fhe_batch_decode, fhe_galois_element and fhe_apply_galois (batched slots and Galois rotations).
+ *      fhe_batch_decode, fhe_galois_element and fhe_apply_galois (batched slots and Galois rotations), and for fhe_block8x8_plan_create /
+ *      destroy, fhe_block8x8_scalar, fhe_channel_mix and fhe_dct8_matrix (integer linear maps across slot-packed ciphertexts).
  * A host compiled against this header compares fhe_abi_version() with FHE_ABI_VERSION before anything else (the Python
  * binding and seal/seal.h do). */
 #define FHE_ABI_VERSION 4
@@ -317,6 +318,49 @@ size_t fhe_apply_galois_scratch_bytes(const fhe_ctx *ctx, uint32_t dbc, uint64_t
 int fhe_apply_galois(const fhe_ctx *ctx, const uint64_t *ct2, uint64_t ct_stride_words, uint64_t *out2, uint64_t out_stride_words,
                      uint64_t count, uint32_t galois_elt, const uint64_t *d_key_ntt, uint32_t dbc, void *scratch, size_t scratch_bytes,
                      fhe_stream stream);
+
+/* ---- integer linear maps ACROSS slot-packed ciphertexts: the packed JPEG transform ------------------------------------------------
+ * A client that packs by POSITION -- ciphertext p = 8 r + c of a group of 64 holds, in slot b, pixel (r, c) of 8x8 block b -- turns the block
+ * DCT, the quantisation, their inverses and the colour conversion into linear maps across ciphertexts with integer SCALAR weights: no
+ * rotation, no key.  New entry points only.
+ *
+ * Scalars.  A scalar is an int64_t w; it acts on a polynomial as multiply_plain with the one-coefficient plaintext [w mod t], i.e. as the
+ * coefficient-wise product modulo each q_i with the centred lift of w mod t (fhe_multiply_plain_sparse's rule).  Every scalar must satisfy
+ * |w| <= min((t - 1) / 2, 2^31 - 1), so that the lift of w is w itself; anything else is FHE_ERR_PARAM.  Zero entries of a matrix are skipped
+ * terms.  The ring operations are exact and residues canonical, so any order of evaluation and any folding of constants modulo q_i gives the
+ * same bits: "bit-identical" below is to the op-by-op composition of multiply_plain and add.
+ *
+ * fhe_block8x8_scalar: in, out [count][64][size][k][n], size >= 2 polynomials per ciphertext; ciphertext 8 x + y of a group is X[x][y].  For
+ * every polynomial, prime and coefficient
+ *     Y[u][v] = post[u][v] * sum_x sum_y L[u][x] * R[v][y] * pre[x][y] * X[x][y]        (mod q_i, canonical)
+ * bit-identical to: pre per input, L down the columns, R along the rows, post per output.  L, R, pre, post: [64] row-major host arrays;
+ * pre / post == NULL mean all ones.  fhe_block8x8_plan_create refuses (FHE_ERR_PARAM) a zero entry of pre or post, an all-zero row of L or R
+ * (an output that would be the transparent zero), a scalar out of range and a null pointer; fhe_block8x8_scalar refuses size < 2,
+ * size > FHE_MAX_POLYS, a null pointer, a plan of another context and an output that overlaps the input without being it -- all before
+ * anything is enqueued.  out == in is allowed; count == 0 is a no-op.  No scratch: one kernel reads each input word once and writes each output
+ * word once (csrc/packed.hip).  The plan
+ * keeps 4 x 64 constants per prime on the device and belongs to its context. */
+typedef struct fhe_block8x8_plan fhe_block8x8_plan;
+int fhe_block8x8_plan_create(const fhe_ctx *ctx, const int64_t *L, const int64_t *R, const int64_t *pre, const int64_t *post, fhe_stream stream,
+                             fhe_block8x8_plan **out);
+int fhe_block8x8_plan_destroy(fhe_block8x8_plan *plan);
+int fhe_block8x8_scalar(const fhe_ctx *ctx, const fhe_block8x8_plan *plan, const uint64_t *in, uint64_t *out, uint32_t size, uint64_t count,
+                        fhe_stream stream);
+/* out_i = sum_j M[i][j] * in_j for `count` ciphertexts of `size` polynomials in each of c input and m output planes, 1 <= c, m <= 8 (M: [m][c]
+ * row-major host scalars): ciphertext e of input channel j starts at in + e * in_ct_stride_words + j * in_plane_stride_words, outputs likewise
+ * (interleaved and planar layouts are both strides).  With bias != NULL, fhe_add_plain with the one-coefficient plaintext [bias_i mod t],
+ * sign +1, follows on output plane i (the bias range is the scalar range; a zero bias adds nothing).  An all-zero row of M is refused.  In
+ * place is allowed when the pointers and strides are identical and m == c; any other overlap of the input and output ranges, and strides that
+ * let two ciphertexts of one operand overlap, are refused.  count == 0 is a no-op. */
+int fhe_channel_mix(const fhe_ctx *ctx, const int64_t *M, const int64_t *bias, uint32_t c, uint32_t m, const uint64_t *in,
+                    uint64_t in_ct_stride_words, uint64_t in_plane_stride_words, uint64_t *out, uint64_t out_ct_stride_words,
+                    uint64_t out_plane_stride_words, uint32_t size, uint64_t count, fhe_stream stream);
+/* Host only: D[u][x] = round-half-away-from-zero(2^bits * c_u / 2 * cos((2 x + 1) u pi / 16)), c_0 = 1 / sqrt(2), c_u = 1 otherwise -- the
+ * orthonormal 8-point DCT-II in `bits` fractional bits, 1 <= bits <= 20, D: [64] row-major.  bits = 8: row 0 is eight times 91, row 1 is
+ * 126, 106, 71, 25, -25, -71, -106, -126.  Row u is (-1)^u-symmetric.  The fixed-point transform built from it (circuits.packed_dct_plan) is a
+ * transform of its own: its ciphertexts and decrypted values are NOT those of fhe_dct8x8_quant below, which follows the reference's
+ * FractionalEncoder circuit. */
+int fhe_dct8_matrix(int bits, int64_t *D);
 
 /* ---- fused block circuit: encrypted_dct (homo/fhe_image.h:196-288) followed by quantize_fhe
  * (homo/fhe_image.h:294-305) on n_blocks independent 8x8 blocks.  in/out: [n_blocks][64][2][k][n].
