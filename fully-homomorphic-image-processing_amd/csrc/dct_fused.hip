@@ -17,6 +17,11 @@
 //                       40 bytes per thread and polynomial for primes <= 37 bits, FP64 otherwise)
 //   kernel B (columns): same for columns on the NTT-form intermediates, per-output scale
 //                       encode(0.125)*encode(1/quant) folded into one product, inverse NTT, store.
+// The public u64 ciphertexts are read and written 8 bytes per lane (a thread owns coefficients r*TP + tid, never two
+// neighbours).  The private formats are laid out so that the column kernel moves 16 bytes per lane (`buffer_load_dwordx4`,
+// 1 KiB contiguous per wave): the packed intermediate as two 16-byte planes of low words and one 8-byte plane of high
+// bytes (store_packed), the FP64 intermediate as planes of value pairs, the packed column kernel's constants as tables of
+// pairs (k_consts_to_pairs).  Slot ownership, the transforms and every arithmetic operation are those of the 8-byte layout.
 // Each workgroup carries 4 polynomials x 2^LE coefficients per thread in registers (n = 4096: LE = 3,
 // 512 threads, 64 data VGPRs, two workgroups = four waves per SIMD) and shares every twiddle across
 // the four; the even and odd workgroup of a line read the same eight inputs and are placed on the
@@ -216,13 +221,18 @@ __device__ __forceinline__ void ntt_inv(double (&x)[M][1 << LE], double (&w)[(1 
 // Packed intermediate (primes <= 37 bits): a row output is an integer |v| < 2^39, so it travels as
 // its low 32 bits plus one signed high byte -- 40 bytes per thread and polynomial instead of 64.
 // t = v + (2^52 + 2^51) has bits(t) = (0x43380000 + floor(v / 2^32)) : (v mod 2^32), so packing is one
-// FP64 add and byte picks, unpacking (cols_body) rebuilds t from (low word, 0x43380000 + sign-extended byte),
-// and the column kernel's first butterfly works on the biased values directly:
-//   t_a - t_b = a - b,   t_a + (t_b - 2 (2^52 + 2^51)) = a + b      (all exact).
+// FP64 add and byte picks, unpacking (cols_body) rebuilds t from (low word, 0x43380000 + sign-extended byte:
+// one `v_add_u32_sdwa`), and the column kernel's first butterfly works on the biased values directly:
+//   t_a - t_b = a - b,   t_a + (t_b - 2 (2^52 + 2^51)) = a + b
+// (all exact: every operand and result is an integer below 2^53).
+// Layout of a thread's 40 bytes per polynomial (a private format; TP threads): low words 0..3 at tid * 16, low words
+// 4..7 at TP * 16 + tid * 16, the eight high bytes at 2 * TP * 16 + tid * 8 -- so the column kernel fetches a polynomial
+// with two 16-byte loads and one 8-byte load (a wave reads 1 KiB contiguously per 16-byte load).
 constexpr double PACK_BIAS = 6755399441055744.0;
-// `ob` is the workgroup's uniform base, `vo` the thread's and `so` the uniform byte offset.  This one access keeps a
-// plain pointer: with buffer stores here hipcc spills 45-58 VGPRs of the row kernel in every arrangement tried
-// (profiles/EXPERIMENTS.md section 15), with a __restrict__ pointer none.
+// `ob` is the workgroup's uniform base, `vo` the thread's byte offset tid * 8 and `so` the uniform byte offset.  This one
+// access keeps a plain pointer and 8-byte stores (hipcc merges some of them): with buffer stores, or with the four low words
+// of a plane gathered for one 16-byte store, hipcc spills 39-58 VGPRs of the row kernel in every arrangement tried
+// (profiles/EXPERIMENTS.md sections 15 and 19), this form none.
 template <int E, int TP>
 __device__ __forceinline__ void store_packed(char *__restrict__ ob, u32 vo, u32 so, const double (&x)[E]) {
     static_assert(E == 8, "packed layout is defined for 8 values per thread");
@@ -233,8 +243,6 @@ __device__ __forceinline__ void store_packed(char *__restrict__ ob, u32 vo, u32 
         lo[r] = (u32)__double2loint(t);
         hi[r] = (u32)__double2hiint(t);
     }
-#pragma unroll
-    for (int q = 0; q < 4; q++) *(u64 *)(ob + (size_t)(so + q * TP * 8) + vo) = (u64)lo[2 * q] | ((u64)lo[2 * q + 1] << 32);
     u32 h[2];
 #pragma unroll
     for (int g = 0; g < 2; g++) {
@@ -242,6 +250,8 @@ __device__ __forceinline__ void store_packed(char *__restrict__ ob, u32 vo, u32 
         const u32 p23 = __builtin_amdgcn_perm(hi[4 * g + 3], hi[4 * g + 2], 0x0c0c0400u);
         h[g] = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
     }
+#pragma unroll
+    for (int q = 0; q < 4; q++) *(u64 *)(ob + (size_t)(so + (q >> 1) * TP * 16 + (q & 1) * 8) + 2 * vo) = (u64)lo[2 * q] | ((u64)lo[2 * q + 1] << 32);
     *(u64 *)(ob + (size_t)(so + 4 * TP * 8) + vo) = (u64)h[0] | ((u64)h[1] << 32);
 }
 // Circuit constants through LDS (gfx950 `buffer_load_dwordx4 ... lds`): the per-slot constants of a wave -- NT tables x 64
@@ -378,8 +388,15 @@ __device__ __forceinline__ void rows_body(const u64 *__restrict__ in, double *__
         if constexpr (PACK) {
             store_packed<E, TP>((char *)(mid + base), vo, so, x[m]);
         } else {
+            // plane j holds values 2j, 2j + 1 of every thread.  16 coefficients per thread: the same layout 8 bytes at a time (the
+            // pair of registers a 16-byte store needs costs this register-bound shape 129 spilled VGPRs instead of 91)
+            if constexpr (LE >= 4) {
 #pragma unroll
-            for (int r = 0; r < E; r++) gst_f64(win_mid, vo, so + r * TP * 8, x[m][r]);
+                for (int r = 0; r < E; r++) gst_f64(win_mid, 2 * vo, so + (r >> 1) * TP * 16 + (r & 1) * 8, x[m][r]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < E / 2; j++) gst_f64x2(win_mid, 2 * vo, so + j * TP * 16, x[m][2 * j], x[m][2 * j + 1]);
+            }
         }
     }
 }
@@ -404,7 +421,7 @@ __global__ __launch_bounds__((Shape<L, LE>::TP), (Occ<L, LE>::W)) void k_dct_row
 
 template <int L, int LE, bool BIG, int HALF, bool PACK>
 __device__ __forceinline__ void cols_body(const double *__restrict__ mid, u64 *__restrict__ out, const double *__restrict__ consts,
-                                          const double *__restrict__ itw, const Work &wk, double p, double pinv, u32 k, double *lds) {
+                                          const double *__restrict__ cpairs, const double *__restrict__ itw, const Work &wk, double p, double pinv, u32 k, double *lds) {
     using SH = Shape<L, LE>;
     constexpr int N = SH::N, TP = SH::TP, E = SH::E, NC = HalfC<HALF>::NC, FIRST = HalfC<HALF>::FIRST;
     constexpr int LASTP = SH::NP - 1;
@@ -415,17 +432,39 @@ __device__ __forceinline__ void cols_body(const double *__restrict__ mid, u64 *_
     // windows as in rows_body: a column spans 57 ciphertexts from `base` (rows 8 ciphertexts apart), the constants
     // of this prime 76 tables; all offsets below 2^31 (fhe_dct_f64_launch)
     const gwin_t win_mid = gwin(mid + base), win_out = gwin(out + base);
-    const gwin_t win_c = gwin(consts + (size_t)FIRST * cstride + (size_t)wk.prime * N);
-    // per-output scale: row 2m+HALF, column wk.line -> constant 12 + 8*row + col
-    const gwin_t win_s = gwin(consts + (size_t)(12 + 8 * HALF + wk.line) * cstride + (size_t)wk.prime * N);
+    // constants.  FP64-intermediate variants: win_c = the half's line constants in the plain table, win_s = the per-output
+    // scales (row 2m+HALF, column wk.line -> constant 12 + 8*row + col).  Packed variant: win_c = the half's line pairs in
+    // the paired table (k_consts_to_pairs) from its first one, win_s = the two scale pairs of (column, half), win_1 = the last
+    // line constant of the half (2 or 11), which has no partner and comes from the plain table.
+    const gwin_t win_c = PACK ? gwin(cpairs + 2 * ((size_t)(HALF ? 1 : 0) * cstride + (size_t)wk.prime * N))
+                              : gwin(consts + (size_t)FIRST * cstride + (size_t)wk.prime * N);
+    const gwin_t win_s = PACK ? gwin(cpairs + 2 * ((size_t)(DCT_NPAIR_LINE + 2 * (2 * wk.line + HALF)) * cstride + (size_t)wk.prime * N))
+                              : gwin(consts + (size_t)(12 + 8 * HALF + wk.line) * cstride + (size_t)wk.prime * N);
+    const gwin_t win_1 = gwin(consts + (size_t)(FIRST + NC - 1) * cstride + (size_t)wk.prime * N);
     const u32 vo = (u32)tid * 8u, rsb = (u32)(ct_words * 64), csb = (u32)(cstride * 8);     // bytes per row / per table
     const double pbias = p + 4503599627370496.0;
     double cn[9], sn[4];
     auto fetch = [&](int r) {
+        if constexpr (PACK) {
 #pragma unroll
-        for (int i = 0; i < NC; i++) cn[i] = gld_f64(win_c, vo, (u32)i * csb + r * TP * 8);
+            for (int i = 0; i < NC / 2; i++) {
+                const f64x2 v = gld_f64x2(win_c, 2 * vo, (u32)i * 2 * csb + r * TP * 16);
+                cn[2 * i] = v.a;
+                cn[2 * i + 1] = v.b;
+            }
+            cn[NC - 1] = gld_f64(win_1, vo, r * TP * 8);
 #pragma unroll
-        for (int m = 0; m < 4; m++) sn[m] = gld_f64(win_s, vo, (u32)(16 * m) * csb + r * TP * 8);
+            for (int g = 0; g < 2; g++) {
+                const f64x2 v = gld_f64x2(win_s, 2 * vo, (u32)g * 2 * csb + r * TP * 16);
+                sn[2 * g] = v.a;
+                sn[2 * g + 1] = v.b;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NC; i++) cn[i] = gld_f64(win_c, vo, (u32)i * csb + r * TP * 8);
+#pragma unroll
+            for (int m = 0; m < 4; m++) sn[m] = gld_f64(win_s, vo, (u32)(16 * m) * csb + r * TP * 8);
+        }
     };
     double wl[E - 1];
     if constexpr (!PACK) {           // in flight behind the bulk loads
@@ -437,24 +476,25 @@ __device__ __forceinline__ void cols_body(const double *__restrict__ mid, u64 *_
         // rebuild the biased doubles t = 2^52 + 2^51 + v from (0x43380000 + sign-extended byte : low
         // word) and let the first butterfly remove the bias.  All 80 packed words are requested
         // before the first is used (x is not live yet).
-        u64 wa[4][5], wb[4][5];
+        u32x4 qa[4][2], qb[4][2];
+        u64 ha[4], hb[4];
 #pragma unroll
         for (int m = 0; m < 4; m++) {
 #pragma unroll
-            for (int q = 0; q < 5; q++) {
-                wa[m][q] = gld_u64(win_mid, vo, (u32)m * rsb + q * TP * 8);
-                wb[m][q] = gld_u64(win_mid, vo, (u32)(7 - m) * rsb + q * TP * 8);
+            for (int g = 0; g < 2; g++) {
+                qa[m][g] = gld_b128(win_mid, 2 * vo, (u32)m * rsb + g * TP * 16);
+                qb[m][g] = gld_b128(win_mid, 2 * vo, (u32)(7 - m) * rsb + g * TP * 16);
             }
+            ha[m] = gld_u64(win_mid, vo, (u32)m * rsb + 4 * TP * 8);
+            hb[m] = gld_u64(win_mid, vo, (u32)(7 - m) * rsb + 4 * TP * 8);
         }
 #pragma unroll
         for (int m = 0; m < 4; m++) {
 #pragma unroll
             for (int r = 0; r < E; r++) {
-                const u32 la = (r & 1) ? (u32)(wa[m][r >> 1] >> 32) : (u32)wa[m][r >> 1];
-                const u32 lb = (r & 1) ? (u32)(wb[m][r >> 1] >> 32) : (u32)wb[m][r >> 1];
-                const u32 hwa = (r & 4) ? (u32)(wa[m][4] >> 32) : (u32)wa[m][4], hwb = (r & 4) ? (u32)(wb[m][4] >> 32) : (u32)wb[m][4];
-                const double ta = __hiloint2double((int)(0x43380000u + (u32)(int)(signed char)(hwa >> (8 * (r & 3)))), (int)la);
-                const double tb = __hiloint2double((int)(0x43380000u + (u32)(int)(signed char)(hwb >> (8 * (r & 3)))), (int)lb);
+                const u32 hwa = (r & 4) ? (u32)(ha[m] >> 32) : (u32)ha[m], hwb = (r & 4) ? (u32)(hb[m] >> 32) : (u32)hb[m];
+                const double ta = __hiloint2double((int)(0x43380000u + (u32)(int)(signed char)(hwa >> (8 * (r & 3)))), (int)qa[m][r >> 2][r & 3]);
+                const double tb = __hiloint2double((int)(0x43380000u + (u32)(int)(signed char)(hwb >> (8 * (r & 3)))), (int)qb[m][r >> 2][r & 3]);
                 x[m][r] = HALF ? ta - tb : ta + (tb - 2.0 * PACK_BIAS);
             }
         }
@@ -462,13 +502,13 @@ __device__ __forceinline__ void cols_body(const double *__restrict__ mid, u64 *_
 #pragma unroll
         for (int m = 0; m < 4; m++) {
 #pragma unroll
-            for (int r = 0; r < E; r++) {
-                const double A = gld_f64(win_mid, vo, (u32)m * rsb + r * TP * 8), B = gld_f64(win_mid, vo, (u32)(7 - m) * rsb + r * TP * 8);
-                x[m][r] = HALF ? A - B : A + B;
+            for (int j = 0; j < E / 2; j++) {
+                const f64x2 A = gld_f64x2(win_mid, 2 * vo, (u32)m * rsb + j * TP * 16), B = gld_f64x2(win_mid, 2 * vo, (u32)(7 - m) * rsb + j * TP * 16);
+                x[m][2 * j] = HALF ? A.a - B.a : A.a + B.a;
+                x[m][2 * j + 1] = HALF ? A.b - B.b : A.b + B.b;
             }
         }
     }
-    if constexpr (PACK) load_tw<L, LE, LASTP>(wl, itw, tid);   // the unpacking needs the registers first
 #pragma unroll
     for (int r = 0; r < E; r++) {
         double c[9], sc[4];
@@ -484,6 +524,9 @@ __device__ __forceinline__ void cols_body(const double *__restrict__ mid, u64 *_
 #pragma unroll
         for (int m = 0; m < 4; m++) x[m][r] = y[m];
     }
+    // packed variant: the last pass's twiddles are requested only now -- 14 registers that the slots need for the paired
+    // constants (requested before the slots, the kernel spills 4 VGPRs); four waves per SIMD hide the round trip
+    if constexpr (PACK) load_tw<L, LE, LASTP>(wl, itw, tid);
     int phase = 0;
     ntt_inv<L, LE, 4, BIG>(x, wl, itw, p, pinv, lds, tid, phase);
 #pragma unroll
@@ -495,14 +538,14 @@ __device__ __forceinline__ void cols_body(const double *__restrict__ mid, u64 *_
 
 template <int L, int LE, bool BIG, bool PACK>
 __global__ __launch_bounds__((Shape<L, LE>::TP), (Occ<L, LE>::W)) void k_dct_cols(const double *__restrict__ mid, u64 *__restrict__ out,
-                                                                  const double *__restrict__ consts, const double *__restrict__ itw_all,
+                                                                  const double *__restrict__ consts, const double *__restrict__ cpairs, const double *__restrict__ itw_all,
                                                                   const Modulus *__restrict__ mods, u32 k) {
     __shared__ double lds[2 * Shape<L, LE>::LDS_WORDS];
     const Work wk = decode(blockIdx.x, k);   // line = column index
     const double p = (double)mods[wk.prime].q, pinv = 1.0 / p;
     const double *itw = itw_all + (size_t)wk.prime * Shape<L, LE>::N;
-    if (wk.half) cols_body<L, LE, BIG, 1, PACK>(mid, out, consts, itw, wk, p, pinv, k, lds);
-    else cols_body<L, LE, BIG, 0, PACK>(mid, out, consts, itw, wk, p, pinv, k, lds);
+    if (wk.half) cols_body<L, LE, BIG, 1, PACK>(mid, out, consts, cpairs, itw, wk, p, pinv, k, lds);
+    else cols_body<L, LE, BIG, 0, PACK>(mid, out, consts, cpairs, itw, wk, p, pinv, k, lds);
 }
 
 // EXPERIMENT (round 4, FHE_DCT_ONE_LAUNCH=D; off by default): rows and columns in ONE launch.  A unit is (prime, block,
@@ -515,7 +558,7 @@ __global__ __launch_bounds__((Shape<L, LE>::TP), (Occ<L, LE>::W)) void k_dct_col
 // acquire: atomic load + __threadfence), and a spin that runs out raises *err instead of hanging the device.
 template <int L, int LE>
 __global__ __launch_bounds__((Shape<L, LE>::TP), (Occ<L, LE>::W)) void k_dct_one_launch(const u64 *__restrict__ in, double *__restrict__ mid, u64 *__restrict__ out,
-                                                                        const double *__restrict__ consts, const double *__restrict__ tw_all,
+                                                                        const double *__restrict__ consts, const double *__restrict__ cpairs, const double *__restrict__ tw_all,
                                                                         const double *__restrict__ itw_all, const Modulus *__restrict__ mods, u32 k,
                                                                         u32 n_blocks, u32 dist, u32 *__restrict__ arrived, u32 *__restrict__ err) {
     __shared__ double lds[2 * Shape<L, LE>::LDS_WORDS];
@@ -555,8 +598,8 @@ __global__ __launch_bounds__((Shape<L, LE>::TP), (Occ<L, LE>::W)) void k_dct_one
         }
         __syncthreads();
         const double *itw = itw_all + (size_t)wk.prime * Shape<L, LE>::N;
-        if (wk.half) cols_body<L, LE, false, 1, true>(mid, out, consts, itw, wk, p, pinv, k, lds);
-        else cols_body<L, LE, false, 0, true>(mid, out, consts, itw, wk, p, pinv, k, lds);
+        if (wk.half) cols_body<L, LE, false, 1, true>(mid, out, consts, cpairs, itw, wk, p, pinv, k, lds);
+        else cols_body<L, LE, false, 0, true>(mid, out, consts, cpairs, itw, wk, p, pinv, k, lds);
     }
 }
 
@@ -572,6 +615,32 @@ __global__ void k_consts_to_f64(const ulonglong2 *__restrict__ in, double *__res
     const u64 q = mods[(i / n) % k].q;
     const u64 w = in[rowbase + src].x;
     out[i] = w > q / 2 ? -(double)(q - w) : (double)w;
+}
+
+// The column kernel's tables: two constants that a thread uses in the same slot as ONE 16-byte element, [pair table][prime][position]
+// of double2, so a lane reads both with one `buffer_load_dwordx4` and a wave 1 KiB contiguously.  Pair tables 0..4 are the line
+// constants {0,1} {3,4} {5,6} {7,8} {9,10} (2 and 11 have no partner and stay in the plain table); 5 + 2 (2 col + half) + g holds the
+// output scales of column `col`, half `half`: rows (half, 2 + half) for g = 0 and (4 + half, 6 + half) for g = 1.
+__global__ void k_consts_to_pairs(const ulonglong2 *__restrict__ in, double *__restrict__ out, const Modulus *__restrict__ mods, u32 k, u32 n, u32 le, u32 total) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const u32 pos = i % n, prime = (i / n) % k, pt = i / (n * k);
+    const u32 tp = n >> le, r = pos / tp, t = pos % tp;
+    const u32 j = (t << le) + r;
+    const u32 src = (j & 15) * (n >> 4) + (j >> 4);
+    u32 ca, cb;
+    if (pt < DCT_NPAIR_LINE) {
+        ca = pt ? 2 * pt + 1 : 0;
+        cb = ca + 1;
+    } else {
+        const u32 u = pt - DCT_NPAIR_LINE, g = u & 1, half = (u >> 1) & 1, col = u >> 2;
+        ca = 12 + 8 * (4 * g + half) + col;
+        cb = ca + 16;
+    }
+    const u64 q = mods[prime].q;
+    const u64 wa = in[((size_t)ca * k + prime) * n + src].x, wb = in[((size_t)cb * k + prime) * n + src].x;
+    out[2 * (size_t)i] = wa > q / 2 ? -(double)(q - wa) : (double)wa;
+    out[2 * (size_t)i + 1] = wb > q / 2 ? -(double)(q - wb) : (double)wb;
 }
 
 // rgb_to_ycc_fhe (homo/fhe_image.h:310-325) for one residue polynomial of one pixel: three joint
@@ -739,11 +808,17 @@ bool fhe_dct_f64_supported(const fhe_ctx *c) {
 }
 
 int fhe_dct_f64_make_consts(const fhe_ctx *c, fhe_dct_plan *plan, hipStream_t st) {
-    const u32 total = DCT_NCONST * c->k * c->n;
-    HIP_TRY(hipMalloc(&plan->d_consts_f64, sizeof(double) * total));
+    const u32 total = DCT_NCONST * c->k * c->n, pairs = DCT_NPAIR * c->k * c->n;
     const u32 le = dct_shape_le(c);
+    const bool packed = c->max_prime_bits <= 37 && le == 3 && c->opt.dct_pack;      // the contexts launch_pair runs the packed column kernel for
+    HIP_TRY(hipMalloc(&plan->d_consts_f64, sizeof(double) * total));
+    if (packed) { HIP_TRY(hipMalloc(&plan->d_consts_pair, 2 * sizeof(double) * pairs)); }
     k_consts_to_f64<<<(total + 255) / 256, 256, 0, st>>>(plan->d_consts, plan->d_consts_f64, c->qb.d_mod, c->k, c->n, le, total);
     KERNEL_CHECK();
+    if (packed) {
+        k_consts_to_pairs<<<(pairs + 255) / 256, 256, 0, st>>>(plan->d_consts, plan->d_consts_pair, c->qb.d_mod, c->k, c->n, le, pairs);
+        KERNEL_CHECK();
+    }
     return FHE_OK;
 }
 
@@ -758,14 +833,14 @@ static void launch_pair(const fhe_ctx *c, const fhe_dct_plan *plan, const u64 *i
     if constexpr (LE == 4) {
         if (big) {
             if (which & 1) k_dct_rows<L, LE, true, false, false><<<grid, TP, 0, st>>>(in, mid, plan->d_consts_f64, c->qb.d_tw_f64, c->qb.d_mod, c->k);
-            if (which & 2) k_dct_cols<L, LE, true, false><<<grid, TP, 0, st>>>(mid, out, plan->d_consts_f64, c->qb.d_itw_f64, c->qb.d_mod, c->k);
+            if (which & 2) k_dct_cols<L, LE, true, false><<<grid, TP, 0, st>>>(mid, out, plan->d_consts_f64, plan->d_consts_pair, c->qb.d_itw_f64, c->qb.d_mod, c->k);
             return;
         }
     }
     if constexpr (LE == 3) {
         if (big) {
             if (which & 1) k_dct_rows<L, LE, true, false, false><<<grid, TP, 0, st>>>(in, mid, plan->d_consts_f64, c->qb.d_tw_f64, c->qb.d_mod, c->k);
-            if (which & 2) k_dct_cols<L, LE, true, false><<<grid, TP, 0, st>>>(mid, out, plan->d_consts_f64, c->qb.d_itw_f64, c->qb.d_mod, c->k);
+            if (which & 2) k_dct_cols<L, LE, true, false><<<grid, TP, 0, st>>>(mid, out, plan->d_consts_f64, plan->d_consts_pair, c->qb.d_itw_f64, c->qb.d_mod, c->k);
             return;
         }
         if (c->max_prime_bits <= 37 && c->opt.dct_pack) {      // packed intermediate, 40 instead of 64 bytes
@@ -773,13 +848,13 @@ static void launch_pair(const fhe_ctx *c, const fhe_dct_plan *plan, const u64 *i
                 if (c->opt.dct_ldsc) k_dct_rows<L, LE, false, true, true><<<grid, TP, 0, st>>>(in, mid, plan->d_consts_f64, c->qb.d_tw_f64, c->qb.d_mod, c->k);
                 else k_dct_rows<L, LE, false, true, false><<<grid, TP, 0, st>>>(in, mid, plan->d_consts_f64, c->qb.d_tw_f64, c->qb.d_mod, c->k);
             }
-            if (which & 2) k_dct_cols<L, LE, false, true><<<grid, TP, 0, st>>>(mid, out, plan->d_consts_f64, c->qb.d_itw_f64, c->qb.d_mod, c->k);
+            if (which & 2) k_dct_cols<L, LE, false, true><<<grid, TP, 0, st>>>(mid, out, plan->d_consts_f64, plan->d_consts_pair, c->qb.d_itw_f64, c->qb.d_mod, c->k);
             return;
         }
     }
     {
         if (which & 1) k_dct_rows<L, LE, false, false, false><<<grid, TP, 0, st>>>(in, mid, plan->d_consts_f64, c->qb.d_tw_f64, c->qb.d_mod, c->k);
-        if (which & 2) k_dct_cols<L, LE, false, false><<<grid, TP, 0, st>>>(mid, out, plan->d_consts_f64, c->qb.d_itw_f64, c->qb.d_mod, c->k);
+        if (which & 2) k_dct_cols<L, LE, false, false><<<grid, TP, 0, st>>>(mid, out, plan->d_consts_f64, plan->d_consts_pair, c->qb.d_itw_f64, c->qb.d_mod, c->k);
     }
 }
 
@@ -792,13 +867,16 @@ int fhe_dct_f64_launch(const fhe_ctx *c, const fhe_dct_plan *plan, const u64 *in
     // for k n < 2^21, far beyond any context this path accepts (n <= 8192)
     if ((u64)c->k * c->n >= (1ULL << 21)) return fail(FHE_ERR_PARAM, "fused FP64 path: a block of ciphertexts exceeds the 2 GiB addressing window");
     const bool big = c->max_prime_bits > 40;
+    // the packed column kernel reads the paired tables: a plan without them (made for a context with FHE_DCT_PACK=0) is refused
+    if (!big && dct_shape_le(c) == 3 && c->max_prime_bits <= 37 && c->opt.dct_pack && !plan->d_consts_pair)
+        return fail(FHE_ERR_PARAM, "fused FP64 path: the plan has no paired constant tables (it was created for a context without the packed intermediate)");
     if (c->opt.dct_one_launch && which == 3 && c->logn == 12 && dct_shape_le(c) == 3 && c->max_prime_bits <= 37 && c->opt.dct_pack && c->d_arrived) {
         const u64 n_units = n_blocks * 2 * c->k;
         if (n_units > c->arrived_cap) return fail(FHE_ERR_PARAM, "one-launch experiment: wave too large for the arrival counters");
         HIP_TRY(hipMemsetAsync(c->d_arrived, 0, (n_units + 1) * sizeof(u32), st));
         const u32 dist = c->opt.dct_one_launch;
         const u64 chunks = (n_units + 7) / 8 + (dist & 0xffffu);
-        k_dct_one_launch<12, 3><<<(unsigned)(chunks * 32 * 8), Shape<12, 3>::TP, 0, st>>>(in, mid, out, plan->d_consts_f64, c->qb.d_tw_f64, c->qb.d_itw_f64, c->qb.d_mod,
+        k_dct_one_launch<12, 3><<<(unsigned)(chunks * 32 * 8), Shape<12, 3>::TP, 0, st>>>(in, mid, out, plan->d_consts_f64, plan->d_consts_pair, c->qb.d_tw_f64, c->qb.d_itw_f64, c->qb.d_mod,
                                                                                        c->k, (u32)n_blocks, dist, c->d_arrived + 1, c->d_arrived);
         KERNEL_CHECK();
         // EXPERIMENT path (FHE_DCT_ONE_LAUNCH; profiles/EXPERIMENTS.md section 1; never a default, never in a parity path other than its

@@ -1463,7 +1463,7 @@ extern "C" int fhe_dct_plan_create(const fhe_ctx *c, const double *quant64, int 
     auto cleanup = [&](int code) {
         if (d_eighth) (void)hipFree(d_eighth);
         if (d_tmp) (void)hipFree(d_tmp);
-        if (code) { (void)hipFree(p->d_consts); if (p->d_consts_f64) (void)hipFree(p->d_consts_f64); if (p->d_consts_le3) (void)hipFree(p->d_consts_le3); delete p; }
+        if (code) { (void)hipFree(p->d_consts); if (p->d_consts_f64) (void)hipFree(p->d_consts_f64); if (p->d_consts_pair) (void)hipFree(p->d_consts_pair); if (p->d_consts_le3) (void)hipFree(p->d_consts_le3); delete p; }
         return code;
     };
     auto prep = [&](double v, ulonglong2 *dst) -> int {
@@ -1497,6 +1497,7 @@ extern "C" int fhe_dct_plan_destroy(fhe_dct_plan *p) {
     if (!p) return FHE_OK;
     if (p->d_consts) (void)hipFree(p->d_consts);
     if (p->d_consts_f64) (void)hipFree(p->d_consts_f64);
+    if (p->d_consts_pair) (void)hipFree(p->d_consts_pair);
     if (p->d_consts_le3) (void)hipFree(p->d_consts_le3);
     delete p;
     return FHE_OK;
@@ -1508,7 +1509,8 @@ static u64 dct_wave_blocks(const fhe_ctx *c) { return c->opt.dct_wave_blocks; }
 extern "C" size_t fhe_dct8x8_scratch_bytes(const fhe_ctx *c, uint64_t n_blocks) {
     if (!c || !(fhe_dct_f64_supported(c) || fhe_dct_u64_supported(c))) return 0;
     const u64 wave = dct_wave_blocks(c) < n_blocks ? dct_wave_blocks(c) : n_blocks;
-    return (size_t)wave * 64 * 2 * c->k * c->n * sizeof(double);
+    // + 16: the fused FP64 pair rounds the pointer up to the 16 bytes its wide accesses need (fhe_dct8x8_quant)
+    return (size_t)wave * 64 * 2 * c->k * c->n * sizeof(double) + 16;
 }
 
 extern "C" int fhe_dct_path(const fhe_ctx *c) {
@@ -1526,8 +1528,11 @@ extern "C" int fhe_dct8x8_quant(const fhe_ctx *c, const fhe_dct_plan *plan, cons
     hipStream_t st = (hipStream_t)s;
     if (plan->d_consts_f64 && fhe_dct_f64_supported(c) && !c->opt.force_u64) {
         const size_t per_block = (size_t)64 * 2 * c->k * c->n;
-        const u64 fit = scratch ? scratch_bytes / (per_block * sizeof(double)) : 0;
+        // the kernels move the intermediate 16 bytes per lane: start it at the next multiple of 16 and count what that costs
+        const size_t lost = scratch ? (size_t)(-(uintptr_t)scratch & 15) : 0;
+        const u64 fit = scratch && scratch_bytes > lost ? (scratch_bytes - lost) / (per_block * sizeof(double)) : 0;
         if (fit == 0) return fail(FHE_ERR_PARAM, "scratch too small: need fhe_dct8x8_scratch_bytes()");
+        scratch = (char *)scratch + lost;
         u64 wave = fit < dct_wave_blocks(c) ? fit : dct_wave_blocks(c);
         // measured: 68.1k blocks/s pipelined vs 71.8k plain at 64-block waves, so this is opt-in
         const bool pipelined = c->opt.dct_pipeline && fit >= 2 && n_blocks > wave / 2 && wave >= 2;

@@ -63,6 +63,16 @@ __device__ __forceinline__ u64 gld_u64(gwin_t w, u32 voff, u32 soff) { return __
 __device__ __forceinline__ double gld_f64(gwin_t w, u32 voff, u32 soff) { return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(w, voff, soff, 0)); }
 __device__ __forceinline__ void gst_u64(gwin_t w, u32 voff, u32 soff, u64 v) { __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), w, voff, soff, 0); }
 __device__ __forceinline__ void gst_f64(gwin_t w, u32 voff, u32 soff, double v) { __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), w, voff, soff, 0); }
+// 16 bytes per lane (`buffer_load/store_dwordx4`): the private formats -- intermediates, paired column constants -- keep two
+// words that a thread uses at the same moment next to each other, so one instruction moves both (a wave touches 1 KiB
+// contiguously).  The address base + voff + soff must be a multiple of 16.
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+struct f64x2 { double a, b; };
+__device__ __forceinline__ u32x4 gld_b128(gwin_t w, u32 voff, u32 soff) { return __builtin_amdgcn_raw_buffer_load_b128(w, voff, soff, 0); }
+__device__ __forceinline__ f64x2 gld_f64x2(gwin_t w, u32 voff, u32 soff) { return __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(w, voff, soff, 0)); }
+__device__ __forceinline__ void gst_f64x2(gwin_t w, u32 voff, u32 soff, double a, double b) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f64x2{a, b}), w, voff, soff, 0);
+}
 
 // Even / odd half of one LL&M line (homo/fhe_image.h:215-242) on a single NTT slot.
 // In:  even: x[m] = d_m + d_(7-m) (tmp0..tmp3);  odd: x[m] = d_m - d_(7-m) (tmp7,tmp6,tmp5,tmp4).

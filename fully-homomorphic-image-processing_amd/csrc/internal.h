@@ -117,10 +117,13 @@ struct fhe_ctx {
 };
 
 #define DCT_NCONST 76
+#define DCT_NPAIR_LINE 5                          // line-constant pairs {0,1} {3,4} {5,6} {7,8} {9,10}
+#define DCT_NPAIR (DCT_NPAIR_LINE + 32)            // + two scale pairs per (column, half)
 extern const double kDctConst[12];   // the twelve LL&M constants shared by the forward (fhe_hip.hip) and inverse (idct.hip) lines
 struct fhe_dct_plan {
     ulonglong2 *d_consts = nullptr;   // [DCT_NCONST][k][n] Shoup pairs, slot order
     double *d_consts_f64 = nullptr;   // [DCT_NCONST][k][n] centred doubles (FP64 path), or null
+    double *d_consts_pair = nullptr;  // [DCT_NPAIR][k][n][2] centred doubles: the packed column kernel's paired tables (dct_fused.hip), or null
     ulonglong2 *d_consts_le3 = nullptr;   // [DCT_NCONST][k][n] Shoup pairs in the fused u64 kernels' order (dct_u64.hip), or null
     u32 k = 0, n = 0;
     bool has_quant = false;

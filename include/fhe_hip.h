@@ -371,6 +371,8 @@ int fhe_dct8_matrix(int bits, int64_t *D);
 int fhe_dct_plan_create(const fhe_ctx *ctx, const double *quant64, int int_coeffs, int frac_coeffs,
                         fhe_stream stream, fhe_dct_plan **out);
 int fhe_dct_plan_destroy(fhe_dct_plan *plan);
+/* scratch for fhe_dct8x8_quant: device memory of any 8-byte alignment.  The fused FP64 pair starts its intermediate at the
+ * next multiple of 16 bytes inside it; the size returned includes those 16 bytes of slack (on every path). */
 size_t fhe_dct8x8_scratch_bytes(const fhe_ctx *ctx, uint64_t n_blocks);
 /* which kernels fhe_dct8x8_quant launches for this context (for labels in measurements): 1 = the fused exact-FP64
  * pair k_dct_rows + k_dct_cols (primes < 2^47, n <= 8192), 2 = the fused u64 pair k_dct_rows_u64 + k_dct_cols_u64
