@@ -3,8 +3,10 @@ and one 8-byte plane of high bytes, the FP64 intermediate as planes of
 value pairs, the column kernel's constants as paired tables.  Every case is compared bit for bit with the library's general
 three-launch u64 path (FHE_DCT_FORCE_U64=1), which shares no kernel, layout or table with the fused pair.
 
-Inputs beyond random residues are the patterns that drive the row outputs to both ends of the packed range: the sums
-d_m + d_(7-m) and differences d_m - d_(7-m) of extreme residues, of either sign."""
+Inputs beyond random residues are coefficient patterns of extreme residues (q - 1 or 0 by row and column), which take the
+coefficient-side sums d_m + d_(7-m) and differences d_m - d_(7-m) to their largest magnitudes of either sign.  They do not
+control what the row outputs hold: the row kernel transforms the polynomials first, and at the NTT slots these inputs behave
+like random data.  The inputs that reach both ends of the packed range are built at the slots: tests/test_gpu_dct_slot_extremes.py."""
 import ctypes as C
 
 import pytest
