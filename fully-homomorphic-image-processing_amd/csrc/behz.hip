@@ -495,7 +495,7 @@ __global__ __launch_bounds__(256) void k_behz_floor_back(const u64 *__restrict__
                 const u64 conv_sk = reduce128(acc[e], msk, mu2, sh);
                 const u64 alpha = mul_shoup(conv_sk + msk - f[e][K], ib.x, ib.y, msk);
                 neg[e] = alpha > (msk >> 1);
-                a_abs[e] = neg[e] ? msk - alpha : alpha;                                     // |alpha_sk| <= k
+                a_abs[e] = neg[e] ? msk - alpha : alpha;                                     // |alpha_sk| ~ |v| / B: any value below m_sk / 2
             }
         }
 #pragma unroll
@@ -757,7 +757,7 @@ __device__ __forceinline__ void floor_back_pm_at(const BehzPmDev &T, const u64 *
 #pragma unroll
         for (int e = 0; e < PCPT; e++) conv[e] += pm_acc_reduce(acc[e], mk);             // each below 1.5 m_sk
     }
-    u32 al[PCPT], ah[PCPT];                // |alpha_sk| (at most k for a product; split like the z_j all the same)
+    u32 al[PCPT], ah[PCPT];                // |alpha_sk| ~ |v| / B, up to m_sk / 2 (millions for full-size operands, not k): split like the z_j
     bool neg[PCPT];
     {
         const ulonglong2 ib = T.inv_B_mod_msk;

@@ -483,7 +483,9 @@ def test_multiply_term_limit_of_the_lazy_tensor_sum(fhe, oracle_mod, size):
 
 
 def test_multiply_edge_inputs(fhe, oracle_mod):
-    """zero, q-1 everywhere: extremes of the base conversions"""
+    """zero, and q - 1 everywhere: the wrap cases of the residue-wise tensor sums.  For the base conversions this is the SMALLEST
+    product, not an extreme: q - 1 lifts to the centred value -1, the product is +1 and the fast floor leaves v ~ t / q
+    (their extremes: tests/test_gpu_behz_extremes.py)"""
     ctx, orc = _pair(fhe, oracle_mod, "SMALL")
     ev = fhe.Evaluator(ctx)
     a = np.zeros((1, 2, ctx.k, ctx.n), dtype=np.uint64)
