@@ -951,7 +951,10 @@ __global__ __launch_bounds__(NttShape<L>::TP, 4) void k_relin_fwd_pm(const u64 *
     for (int r = 0; r < 16; r++) x[0][r] = canon_pm(x[0][r], m);
     store_slots<L>(x[0], dig + (u * k + ii) * N, tid);
 }
-// (2) acc[c][pp][ii][s] = sum_{i,d} dig * evk with mulvv_pm products summed as integers (k nd <= 20 terms of at most 6q), one fold
+// (2) acc[c][pp][ii][s] = sum_{power,i,d} dig * evk with mulvv_pm products summed as integers, one fold.  The host admits
+// k nd npow <= 20 terms (relin_pm_ok), each below the class's RQ: 20 x 6 q < 2^62 on class A (55 bits), 20 x 1.5 q = 30 q < 2^63 on
+// class B (58 bits).  Both operands are canonical here, so a term is in fact below 2^b + delta^2 (ntt_core.h mulvv_pm) and a
+// sum below 20.4 q; tests/keyswitch_craft.py builds keys for which every term of every slot is above q.
 template <typename C>
 __global__ __launch_bounds__(256) void k_relin_accum_pm(const u64 *__restrict__ dig, const u64 *__restrict__ evk, u64 *__restrict__ acc,
                                                         RnsBase base, u32 n, u32 nd, u64 count, u32 npow) {
@@ -1010,7 +1013,7 @@ __global__ __launch_bounds__(NttShape<L>::TP, 4) void k_relin_accum_inv_add_pm(c
     u64 acc[1][16], y[16];
 #pragma unroll
     for (int r = 0; r < 16; r++) acc[0][r] = 0;
-    const u32 terms = k * nd;                            // (i, d) pairs, at most 20: 20 x 6q < 2^62 on a 55-bit base (the host passes nd x powers as nd)
+    const u32 terms = k * nd;                            // (power, i, d) triples, at most 20 (the host passes nd x powers as nd): 20 x 6 q < 2^62 on class A, 20 x 1.5 q < 2^63 on class B
     for (u32 t = 0; t < terms; t++) {
         const u64 *pa = dig + ((c * terms + t) * k + ii) * N + tid, *pb = evk + (((u64)t * 2 + pp) * k + ii) * N + tid;
         u64 xa[16], xb[16];

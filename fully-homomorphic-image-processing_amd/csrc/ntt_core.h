@@ -395,7 +395,11 @@ __device__ __forceinline__ u64 fold_pm(u64 x, const PmMod &m) {
 }
 // a b mod q for a below 2^(b+1) (a folded value) and a canonical b, neither with a prepared companion: the 128-bit
 // product (four multiply-adds), then two folds of its part above 2^b (three multiply-adds).  Result below
-// 2^b + 2^(85-b) delta, which the host checks against the class's RQ.
+// 2^b + 2^(85-b) delta, which the host checks against the class's RQ.  That figure is generous: the first fold leaves
+// V < 2^b + 2^(b+1) delta, so the second adds at most floor(V / 2^b) delta <= 2 delta^2 -- the result is below 2^b + 2 delta^2, and below
+// 2^b + delta^2 for a canonical a (1.018 q on SEAL's 54-bit primes against the 3.09 q of the checked figure, (1 + 2^-8) q on
+// a 58-bit prime with delta < 2^25; tests/test_keyswitch_craft_cpu.py asserts both on the integer model and prints the largest
+// products it finds).
 __device__ __forceinline__ u64 mulvv_pm(u64 a, u64 b, const PmMod &m) {
     const u32 al = (u32)a, ah = (u32)(a >> 32), bl = (u32)b, bh = (u32)(b >> 32);
     const u64 P0 = (u64)al * bl;
