@@ -832,7 +832,9 @@ def test_u64_lazy_ranges_at_boundary_prime_sizes(fhe, oracle_mod, bits, n):
     """The u64 kernels choose their lazy ranges by prime size (csrc/ntt_core.h, csrc/dct_u64.hip): no conditional
     subtraction in the forward butterflies up to 58 bits (values grow to (2 + 4 log2 n) q, which must stay below 2^64),
     doubled Harvey ranges [0, 8q) above; the fused u64 DCT is lazy up to 56 bits and keeps one subtraction per
-    butterfly at 57.  The LARGEST prime of each size with all-(q-1) inputs is the worst case of every bound."""
+    butterfly at 57.  The LARGEST prime of each size with all-(q-1) inputs: the largest INPUTS the kernels take -- not the worst
+    case of the lazy ranges (random data comes closer to the static bounds in almost every stage); the transforms at
+    their arithmetic edges are in tests/test_gpu_ntt_extremes.py."""
     q = [_largest_ntt_prime_below(bits, n), _largest_ntt_prime_below(bits - 1, n)]
     ctx, orc = fhe.SEALContext(n, q, 1 << 14), oracle_mod.Oracle(n, q, 1 << 14)
     ev = fhe.Evaluator(ctx)
