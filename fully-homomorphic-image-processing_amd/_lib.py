@@ -92,6 +92,10 @@ SIGNATURES = {
     "fhe_block8x8_scalar": (_i, [_vp, _vp, _vp, _vp, _u32, _u64, _vp]),
     "fhe_channel_mix": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, _u64, _u64, _vp, _u64, _u64, _u32, _u64, _vp]),
     "fhe_dct8_matrix": (_i, [_i, _vp]),
+    "fhe_plane_map_plan_create": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp, C.POINTER(_vp)]),
+    "fhe_plane_map_plan_destroy": (_i, [_vp]),
+    "fhe_plane_map_plan_info": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u64), C.POINTER(_u32)]),
+    "fhe_plane_map": (_i, [_vp, _vp, _vp, _vp, _u32, _u64, _vp]),
     "fhe_dct_plan_create": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(_vp)]),
     "fhe_dct_plan_destroy": (_i, [_vp]),
     "fhe_dct8x8_scratch_bytes": (_sz, [_vp, _u64]),

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .evaluator import YQT, Block8x8Plan, FractionalEncoder, PreparedPlain, _ptr, _stream, check_evaluation_keys
+from .evaluator import YQT, Block8x8Plan, FractionalEncoder, PlaneMapPlan, PreparedPlain, _ptr, _stream, check_evaluation_keys
 
 
 class PlainCache:
@@ -700,3 +700,154 @@ def packed_jpeg_compress(ev, plan, r, g, b, colour_bits=8):
     for ch, p in enumerate(plan):
         ev.block8x8_scalar(p.plan, planes[ch], out=planes[ch])
     return planes
+
+
+# ---- packed frames: pixels packed by POSITION (client.pack_frames / pack_tiles), resize and filters as sparse maps across ciphertexts ----
+# Ciphertext p of a frame holds pixel p of n independent frames (or tiles of one image) in its slots.  A resize, a strided filter or a
+# chroma subsampling is then one Evaluator.plane_map per pass: integer scalar weights, no rotation, no key (include/fhe_hip.h
+# "sparse integer maps across position-packed ciphertexts").  Values carry `scale_bits` fractional bits per plan; client.descale rounds
+# them away after decryption.
+class PackedPlanePlan:
+    """The integer map out[o] = sum_p weights[o][p] * in[taps[o][p]] from n_in to n_out position-packed planes, with its fixed-point
+    scale.  ctx None: the integers alone (model, bound), no device plan.  order / window: PlaneMapPlan's."""
+
+    def __init__(self, ctx, n_in, taps, weights, scale_bits=0, order=None, window=0):
+        self.taps = np.ascontiguousarray(np.asarray(taps, dtype=np.uint32))
+        self.weights = np.ascontiguousarray(np.asarray(weights, dtype=np.int64))
+        if self.taps.ndim != 2 or self.taps.shape != self.weights.shape:
+            raise ValueError("PackedPlanePlan: taps and weights must both be [n_out][T], got %r and %r" % (self.taps.shape, self.weights.shape))
+        self.n_in, self.n_out = int(n_in), int(self.taps.shape[0])
+        live = self.weights != 0
+        if live.any() and int(self.taps[live].max()) >= self.n_in:
+            raise ValueError("PackedPlanePlan: a live tap is not below n_in = %d" % self.n_in)
+        self.scale_bits = int(scale_bits)
+        self.order = None if order is None else np.ascontiguousarray(np.asarray(order, dtype=np.uint32).reshape(-1))
+        self.ctx = ctx
+        self.plan = None if ctx is None else PlaneMapPlan(ctx, self.n_in, self.taps, self.weights, order=self.order, window=window)
+
+    def model(self, values):
+        """the exact integer map on [n_in, ...] values -> [n_out, ...] (Python integers: no overflow)"""
+        v = np.asarray(values).astype(object)
+        if v.shape[0] != self.n_in:
+            raise ValueError("PackedPlanePlan.model: %d planes for a plan of %d" % (v.shape[0], self.n_in))
+        out = np.zeros((self.n_out,) + v.shape[1:], dtype=object)
+        w = self.weights.astype(object)
+        for p in range(self.taps.shape[1]):
+            wp = w[:, p].reshape((-1,) + (1,) * (v.ndim - 1))
+            out = out + wp * v[np.where(self.weights[:, p] != 0, self.taps[:, p], 0)]
+        return out
+
+    def bound(self, input_bound):
+        """the exact worst-case |slot value| of any output for inputs of magnitude at most input_bound (a number, or [n_in] per plane):
+        max over o of sum_p |weights[o][p]| bound[taps[o][p]]; the client picks t > 2 * bound"""
+        b = np.broadcast_to(np.asarray(input_bound, dtype=object), (self.n_in,))
+        w = np.abs(self.weights).astype(object)
+        tp = np.where(self.weights != 0, self.taps, 0)
+        return int((w * b[tp]).sum(axis=1).max())
+
+
+def _int_axis(src_len, dst_len, kernel, antialias, convention, weight_bits):
+    """(taps [dst][T] clamped, integer weights [dst][T] summing to 2^weight_bits) of one axis"""
+    bits = int(weight_bits)
+    if not 1 <= bits <= 30:
+        raise ValueError("packed resize: weight_bits = %r (1 .. 30: the weights are integers w * 2^bits)" % (weight_bits,))
+    taps, w = resample_axis_plan(src_len, dst_len, kernel, antialias, convention, bits)
+    wi = np.rint(w * float(1 << bits)).astype(np.int64)               # exact: every weight is a multiple of 2^-bits
+    assert np.array_equal(wi.astype(np.float64) / float(1 << bits), w) and (wi.sum(axis=1) == (1 << bits)).all()
+    return taps.astype(np.int64), wi
+
+
+def _resize_pair(ctx, tx, wx, ty, wy, src_w, src_h, bits, window):
+    """the horizontal and the vertical PackedPlanePlan of a separable map: axis taps tx [dst_w][Tx] into src_w, ty [dst_h][Ty] into src_h"""
+    dst_w, dst_h = tx.shape[0], ty.shape[0]
+    line = np.arange(src_h, dtype=np.int64)
+    th = (line[:, None, None] * src_w + tx[None, :, :]).reshape(src_h * dst_w, -1)
+    wh = np.broadcast_to(wx[None, :, :], (src_h,) + wx.shape).reshape(src_h * dst_w, -1)
+    col = np.arange(dst_w, dtype=np.int64)
+    tv = (ty[:, None, :] * dst_w + col[None, :, None]).reshape(dst_h * dst_w, -1)
+    wv = np.broadcast_to(wy[:, None, :], (dst_h, dst_w, wy.shape[1])).reshape(dst_h * dst_w, -1)
+    order = (np.arange(dst_h, dtype=np.int64)[None, :] * dst_w + col[:, None]).reshape(-1)       # column-major: a window holds whole columns
+    h = PackedPlanePlan(ctx, src_h * src_w, th, wh, bits, window=window)
+    v = PackedPlanePlan(ctx, src_h * dst_w, tv, wv, bits, order=order, window=window)
+    return h, v
+
+
+def packed_resize_plans(ctx, src_w, src_h, dst_w, dst_h, kernel="catmull_rom", antialias=False, convention="half_pixel", weight_bits=8, window=0):
+    """(horizontal, vertical): the two PackedPlanePlans of a separable resize of position-packed frames, row-major planes
+    [src_h * src_w] -> [src_h * dst_w] -> [dst_h * dst_w].  Each axis is resample_axis_plan with weight_bits: its weights are multiples of
+    2^-weight_bits that sum to exactly 1, the integer weights are w * 2^weight_bits; each pass carries scale_bits = weight_bits.  The
+    vertical plan cuts its groups along columns."""
+    tx, wx = _int_axis(src_w, dst_w, kernel, antialias, convention, weight_bits)
+    ty, wy = _int_axis(src_h, dst_h, kernel, antialias, convention, weight_bits)
+    return _resize_pair(ctx, tx, wx, ty, wy, src_w, src_h, int(weight_bits), window)
+
+
+def packed_resize(ev, plans, ct):
+    """both passes on frames [..., src_h * src_w, size, k, n] -> [..., dst_h * dst_w, size, k, n]; the slots hold pixels times
+    2^(plans[0].scale_bits + plans[1].scale_bits)"""
+    return ev.plane_map(plans[1].plan, ev.plane_map(plans[0].plan, ct))
+
+
+def packed_filter_integer(name):
+    """the integer form of a named kernel of FILTERS: dict(weights int64 [kh][kw], divisor, anchor, stride) with weights / divisor the
+    float kernel"""
+    f = FILTERS[name]
+    for div in (1, 4, 9, 16, 256):
+        w = f["weights"] * div
+        if np.allclose(w, np.rint(w), atol=1e-9):
+            return dict(weights=np.rint(w).astype(np.int64), divisor=div, anchor=f["anchor"], stride=f["stride"])
+    raise ValueError("filter %r has no small integer form" % name)
+
+
+def packed_tile_filter_plan(ctx, tile_w, tile_h, weights_int, kw, kh, anchor=None, stride=(1, 1), window=0):
+    """A kw x kh filter with public INTEGER weights over position-packed tiles of tile_w x tile_h pixels, clamp-to-edge, the tap geometry
+    of filter_tap_plan: planes [tile_h * tile_w] -> [dst_h * dst_w], dst = ceil(tile / stride) per axis (.dst_w, .dst_h); scale_bits 0 --
+    dividing by the kernel's divisor is the client's."""
+    w = np.asarray(weights_int, dtype=np.int64).reshape(-1)
+    if w.size != kw * kh:
+        raise ValueError("packed_tile_filter_plan: %d weights for a %d x %d kernel" % (w.size, kw, kh))
+    taps, dst_w, dst_h = filter_tap_plan(tile_w, tile_h, kw, kh, 1, anchor, stride)
+    plan = PackedPlanePlan(ctx, tile_w * tile_h, taps, np.broadcast_to(w[None, :], taps.shape), 0, window=window)
+    plan.dst_w, plan.dst_h = dst_w, dst_h
+    return plan
+
+
+def _tile_axis(src_len, dst_len, core, kernel, antialias, convention, weight_bits):
+    """one axis of packed_tile_resize_plans: (frame taps [core_out][T], weights [core_out][T], halo, core_out)"""
+    if core <= 0 or src_len % core or (core * dst_len) % src_len:
+        raise ValueError("tile resize: a core of %d source samples does not cut %d -> %d into equal tiles (core must divide the source, core * dst / src "
+                         "must be an integer)" % (core, src_len, dst_len))
+    oc = core * dst_len // src_len
+    taps, w = _int_axis(src_len, dst_len, kernel, antialias, convention, weight_bits)
+    T = taps.shape[1]
+    # the taps of an output are first + p, clamped to the edge: where two neighbours differ, the second one is not clamped
+    first = np.zeros(dst_len, dtype=np.int64)
+    for x in range(dst_len):
+        step = np.nonzero(np.diff(taps[x]))[0]
+        first[x] = taps[x][0] if T == 1 else (taps[x][step[0] + 1] - (step[0] + 1) if step.size else (taps[x][0] - (T - 1) if taps[x][0] == 0 else taps[x][0]))
+    raw = first[:, None] + np.arange(T, dtype=np.int64)[None, :]
+    assert np.array_equal(np.clip(raw, 0, src_len - 1), taps)
+    live = w != 0
+    s0 = (np.arange(dst_len) // oc * core)[:, None]
+    reach = np.maximum(np.maximum(s0 - raw, raw - (s0 + core - 1)), 0)
+    halo = int(reach[live].max())
+    rebased = np.where(live, raw - (s0 - halo), 0).reshape(dst_len // oc, oc, T)
+    wt = w.reshape(dst_len // oc, oc, T)
+    if not ((rebased == rebased[:1]).all() and (wt == wt[:1]).all()):
+        raise ValueError("tile resize: the tiles of a core of %d source samples (%d -> %d) do not share one plan: their taps or weights differ"
+                         % (core, src_len, dst_len))
+    return rebased[0], wt[0], halo, oc
+
+
+def packed_tile_resize_plans(src_w, src_h, dst_w, dst_h, core_w, core_h, kernel="catmull_rom", antialias=False, convention="half_pixel", weight_bits=8,
+                             ctx=None, window=0):
+    """A large image resized as overlapping tiles in the slots (client.pack_tiles): returns (horizontal, vertical, halo, core_out).  The
+    whole-image axis plans are cut into tiles of core_w x core_h source pixels; the outputs of a tile's core have their taps rebased to
+    the tile frame, the core plus `halo` = (halo_x, halo_y) pixels on every side (the largest reach of any tap; the image border is the
+    client's clamp-to-edge padding).  One pair of frame plans serves every tile: ValueError unless every tile's rebased taps and weights
+    are identical (core * dst / src must be an integer per axis).  Planes [(core_h + 2 halo_y) * (core_w + 2 halo_x)] ->
+    [core_out_h * core_out_w]; core_out = (w, h) of a tile's output, which client.unpack_tiles stitches."""
+    tx, wx, hx, ow = _tile_axis(src_w, dst_w, core_w, kernel, antialias, convention, weight_bits)
+    ty, wy, hy, oh = _tile_axis(src_h, dst_h, core_h, kernel, antialias, convention, weight_bits)
+    h, v = _resize_pair(ctx, tx, wx, ty, wy, core_w + 2 * hx, core_h + 2 * hy, int(weight_bits), window)
+    return h, v, (hx, hy), (ow, oh)

@@ -392,6 +392,61 @@ def unpack_blocks(slots, width, height):
     return out
 
 
+# ---- position-packed frames and tiles (include/fhe_hip.h "sparse integer maps across position-packed ciphertexts"; circuits.packed_resize_plans)
+def pack_frames(frames, n, t=None):
+    """[groups][planes][n] slot values: frame b of `frames` ([count, ...]: every frame flattened row-major to `planes` pixels) goes to
+    group b // n, slot b % n; pixel p of the frame names the ciphertext; unused slots are 0.  int64, or uint64 reduced modulo t."""
+    a = np.asarray(frames).astype(np.int64)
+    a = a.reshape(a.shape[0], -1)
+    groups = max(1, (a.shape[0] + n - 1) // n)
+    out = np.zeros((groups, a.shape[1], n), dtype=np.int64)
+    for g in range(groups):
+        part = a[g * n:(g + 1) * n]
+        out[g, :, :part.shape[0]] = part.T
+    return out if t is None else (out % np.int64(t)).astype(np.uint64)
+
+
+def unpack_frames(slots, count, shape=None):
+    """the inverse of pack_frames: [groups][planes][n] values -> [count, planes], or [count] + shape"""
+    a = np.asarray(slots)
+    frames = a.transpose(0, 2, 1).reshape(-1, a.shape[1])[:count]
+    return frames if shape is None else frames.reshape((count,) + tuple(shape))
+
+
+def _halo(halo):
+    return (int(halo), int(halo)) if np.isscalar(halo) else (int(halo[0]), int(halo[1]))
+
+
+def pack_tiles(channel, core_w, core_h, halo, n, t=None):
+    """[groups][planes][n] slot values of one image cut into tiles: tile b (raster order over ceil(W / core_w) x ceil(H / core_h) cores)
+    goes to group b // n, slot b % n, as a frame of (core_h + 2 halo_y) x (core_w + 2 halo_x) pixels, row-major: its core with `halo`
+    (a number, or (halo_x, halo_y)) pixels on every side, clamp-to-edge at the image border."""
+    a = np.asarray(channel).astype(np.int64)
+    h, w = a.shape
+    hx, hy = _halo(halo)
+    tw, th = (w + core_w - 1) // core_w, (h + core_h - 1) // core_h
+    frames = np.empty((tw * th, core_h + 2 * hy, core_w + 2 * hx), dtype=np.int64)
+    for b in range(tw * th):
+        j, i = divmod(b, tw)
+        ys = np.clip(np.arange(j * core_h - hy, (j + 1) * core_h + hy), 0, h - 1)
+        xs = np.clip(np.arange(i * core_w - hx, (i + 1) * core_w + hx), 0, w - 1)
+        frames[b] = a[np.ix_(ys, xs)]
+    return pack_frames(frames, n, t)
+
+
+def unpack_tiles(slots, width, height, core_w, core_h):
+    """stitches tiles of core_w x core_h pixels ([groups][core_h * core_w][n], tile b in group b // n, slot b % n, raster order) into
+    [height][width]; what a partial tile holds beyond the image is dropped"""
+    a = np.asarray(slots)
+    tw, th = (width + core_w - 1) // core_w, (height + core_h - 1) // core_h
+    tiles = unpack_frames(a, tw * th, (core_h, core_w))
+    out = np.zeros((th * core_h, tw * core_w), dtype=a.dtype)
+    for b in range(tw * th):
+        j, i = divmod(b, tw)
+        out[j * core_h:(j + 1) * core_h, i * core_w:(i + 1) * core_w] = tiles[b]
+    return out[:height, :width]
+
+
 def descale(values, scale_bits, t):
     """slot values modulo t -> integers: centred modulo t, divided by 2^scale_bits, rounded half away from zero (int64 for t < 2^63)"""
     v = np.asarray(values).astype(object) % int(t)

@@ -246,6 +246,8 @@ extern "C" int fhe_ctx_create(uint32_t n, const uint64_t *q, uint32_t k, uint64_
         o.filter_xcd = !off("FHE_FILTER_XCD");
         o.galois_staged = env_on("FHE_GALOIS_STAGED");
         o.galois_gather_lds = env_on("FHE_GALOIS_GATHER_LDS");
+        o.planemap_direct = env_on("FHE_PLANEMAP_DIRECT");
+        if (const char *e = getenv("FHE_PLANEMAP_WINDOW")) { const int v = atoi(e); if (v == 16 || v == 32 || v == 64) o.planemap_window = (u32)v; }
         o.relin_steps = env_on("FHE_RELIN_STEPS");
         o.enc_unfused = env_on("FHE_ENC_UNFUSED");
         { const char *e = std::getenv("FHE_ENC_OCC"); o.enc_occ4 = e && e[0] == '4'; }

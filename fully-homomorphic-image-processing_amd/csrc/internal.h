@@ -70,6 +70,9 @@ struct FheOptions {
     bool filter_xcd = true;          // FHE_FILTER_XCD=0: fhe_filter2d hands its workgroups out in plain order (every eighth output per XCD) instead of one contiguous run of outputs per XCD
     bool galois_staged = false;      // FHE_GALOIS_STAGED=1: fhe_apply_galois writes [sigma(c0), 0, sigma(c1)] to scratch and runs the plain key switch on it (galois.hip: the correctness baseline)
     bool galois_gather_lds = false;  // FHE_GALOIS_GATHER_LDS=1: the fused digit kernel reads sigma(c1) with coalesced loads into LDS + permuted LDS reads instead of permuted global loads (measured 2-4 % slower at P8192)
+    bool planemap_direct = false;    // FHE_PLANEMAP_DIRECT=1: fhe_plane_map runs the direct kernel (one thread per (output plane, word), sources from global memory) for every plan
+    u32 planemap_window = 0;         // FHE_PLANEMAP_WINDOW=16|32|64: plans created with window = 0 are cut with this window and run the windowed kernel (default: they run the
+                                     // direct kernel, which measured faster in two of six cases; planemap.hip)
     bool behz_fused_prepare = false; // FHE_BEHZ_FUSED_PREPARE=1: base extension fused into the forward transforms (k_behz_prepare_pm: 25 % less HBM traffic per
                                      // product, 5 % slower -- the y_i are recomputed per auxiliary prime and the kernels are issue-bound; profiles/EXPERIMENTS.md)
 };

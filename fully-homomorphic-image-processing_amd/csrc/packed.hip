@@ -17,7 +17,7 @@
 // them below 32 q_i <= 2^63 for primes of at most 58 bits -- every class the presets use -- and go unreduced into the next product.
 // Eight lazy products of a 61-bit prime do not fit 64 bits: contexts with a wider prime, and contexts created with FHE_NTT_NOPM=1, take
 // canonical products (below q_i; eight below 2^64 for q_i < 2^61).  The last product (post, or 1) is reduced to [0, q_i).
-#include "internal.h"
+#include "packed_arith.h"
 
 #include <cmath>
 #include <vector>
@@ -25,34 +25,6 @@
 namespace {
 
 struct B8Tab { ulonglong2 pre[64], L[64], R[64], post[64]; };      // per prime: (w mod q, Shoup companion)
-struct PkMods { u64 q[FHE_MAX_K]; };                               // by value (wave-uniform)
-
-template <bool LAZY>
-struct PkArith {
-    u64 q, nq;
-    u32 zero;
-    __device__ __forceinline__ PkArith(u64 q_) : q(q_), nq(0 - q_), zero(LAZY ? fhe_opaque_zero : 0) {}
-    // x w mod q + {0 .. 3} q (LAZY) or canonical, for any 64-bit x
-    __device__ __forceinline__ u64 mul(u64 x, ulonglong2 w) const {
-        if constexpr (LAZY) return mul_shoup_lazy4(x, w.x, w.y, nq, zero);
-        else return mul_shoup(x, w.x, w.y, q);
-    }
-    __device__ __forceinline__ u64 canon(u64 x) const {
-        if constexpr (LAZY) return csub(csub(x, 2 * q), q);
-        else return x;
-    }
-};
-
-// The table reads are scalar loads with a wave-uniform address.  Left alone, the compiler shares and clusters them across a whole pass
-// (64 pairs = 256 SGPRs per matrix: hundreds of spills); adding a zero it cannot see through to the pointer before each output makes every
-// output load the eight pairs it uses, next to their use -- 16 KiB of scalar-cache traffic per wave against 64 KiB of vector traffic.
-template <typename P>
-__device__ __forceinline__ const P *fresh(const P *p) {
-    int off = 0;
-    asm volatile("" : "+v"(off));
-    return p + __builtin_amdgcn_readfirstlane(off);
-}
-
 // one line of eight: o[v] = sum_y i[y] M[v][y], each sum below 32 q (LAZY) or 8 q.  The eight pairs of output v + 1 are requested before
 // the products of output v, so their scalar-load latency is covered by about a hundred vector instructions (two sets of 32 SGPRs).
 template <bool LAZY>
@@ -153,27 +125,6 @@ __global__ __launch_bounds__(256) void k_channel_mix(const u64 *in, u64 in_cs, u
             }
         }
     }
-}
-
-// |w| <= min((t - 1) / 2, 2^31 - 1): the centred lift of w mod t is w itself
-bool scalar_ok(const fhe_ctx *c, int64_t w) {
-    const u64 a = w < 0 ? (u64)0 - (u64)w : (u64)w;
-    return a <= (c->t - 1) / 2 && a <= 0x7fffffffULL;
-}
-ulonglong2 lift_pair(int64_t w, u64 q) {
-    const u64 a = (w < 0 ? (u64)0 - (u64)w : (u64)w) % q;
-    const u64 r = (w < 0 && a) ? q - a : a;
-    return make_ulonglong2(r, (u64)(((unsigned __int128)r << 64) / q));
-}
-bool lazy_ok(const fhe_ctx *c) { return c->max_prime_bits <= 58 && !c->opt.ntt_nopm; }
-PkMods pk_mods(const fhe_ctx *c) {
-    PkMods M{};
-    for (u32 i = 0; i < c->k; i++) M.q[i] = c->qb.primes[i];
-    return M;
-}
-bool overlap(const void *a, u64 a_words, const void *b, u64 b_words) {
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + a_words * 8, b0 = (uintptr_t)b, b1 = b0 + b_words * 8;
-    return a0 < b1 && b0 < a1;
 }
 
 }  // namespace

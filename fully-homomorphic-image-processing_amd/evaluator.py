@@ -350,6 +350,41 @@ class Block8x8Plan:
             self.h = None
 
 
+class PlaneMapPlan:
+    """Constants of fhe_plane_map (include/fhe_hip.h "sparse integer maps across position-packed ciphertexts"): output plane o is the sum
+    over its slots p of weights[o][p] * plane taps[o][p] of the n_in input planes; taps, weights [n_out][T], T <= 64, zero weights are
+    skipped slots, |w| <= min((t - 1) / 2, 2^31 - 1).  order: the permutation of the outputs the groups are cut along (None: index order);
+    window: 0 (the library's default: the direct kernel, the cut reported for window 16), or 16, 32, 64 (the windowed kernel with that
+    cut).  .groups, .source_reads and .window report the cut."""
+
+    def __init__(self, ctx, n_in, taps, weights, order=None, window=0):
+        taps = np.ascontiguousarray(np.asarray(taps, dtype=np.uint32))
+        weights = np.ascontiguousarray(np.asarray(weights, dtype=np.int64))
+        if taps.ndim != 2 or taps.shape != weights.shape:
+            raise ValueError("PlaneMapPlan: taps and weights must both be [n_out][T], got %r and %r" % (taps.shape, weights.shape))
+        self.ctx, self.n_in, self.n_out, self.T = ctx, int(n_in), int(taps.shape[0]), int(taps.shape[1])
+        self.taps, self.weights = taps, weights
+        self.order = None if order is None else np.ascontiguousarray(np.asarray(order, dtype=np.uint32).reshape(-1))
+        if self.order is not None and self.order.size != self.n_out:
+            raise ValueError("PlaneMapPlan: order holds %d entries for %d outputs" % (self.order.size, self.n_out))
+        h = C.c_void_p()
+        _lib.call("fhe_plane_map_plan_create", ctx.h, self.n_in, self.n_out, self.T, taps.ctypes.data_as(C.c_void_p), weights.ctypes.data_as(C.c_void_p),
+                  None if self.order is None else self.order.ctypes.data_as(C.c_void_p), int(window), _stream(), C.byref(h))
+        self.h = h
+        g, r, w = C.c_uint32(), C.c_uint64(), C.c_uint32()
+        _lib.call("fhe_plane_map_plan_info", h, C.byref(g), C.byref(r), C.byref(w))
+        self.groups, self.source_reads, self.window = int(g.value), int(r.value), int(w.value)
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h:
+            try:
+                _lib.load().fhe_plane_map_plan_destroy(h)
+            except Exception:
+                pass
+            self.h = None
+
+
 def check_evaluation_keys(ctx, evk_ntt, dbc, need, who):
     """The library takes the keys as a bare pointer and reads need * fhe_evk_words(ctx, dbc) words behind it (include/fhe_hip.h): the host
     checks that the tensor it hands over holds them -- a key tensor made for another decomposition bit count (fewer digits), another context or
@@ -660,6 +695,25 @@ class Evaluator:
         Mx = np.ascontiguousarray(Mx)
         _lib.call("fhe_channel_mix", self.ctx.h, Mx.ctypes.data_as(C.c_void_p), None if bv is None else bv.ctypes.data_as(C.c_void_p), c, m,
                   _ptr(planes), ctw, count * ctw, _ptr(out), ctw, count * ctw, size, count, _stream())
+        return out
+
+    def plane_map(self, plan, ct, out=None):
+        """out[..., o] = sum_p weights[o][p] * ct[..., taps[o][p]] on frames of position-packed ciphertexts: ct [..., n_in, size, k, n] ->
+        [..., n_out, size, k, n], bit for bit the multiply_plain / add composition; one kernel (fhe_plane_map).  `out` may not overlap `ct`."""
+        kn = (self.ctx.k, self.ctx.n)
+        if plan.ctx is not self.ctx:
+            raise ValueError("plane_map: the plan was built for another context")
+        if not (isinstance(ct, torch.Tensor) and ct.dim() >= 4 and tuple(ct.shape[-2:]) == kn and ct.shape[-4] == plan.n_in and ct.dtype == torch.int64
+                and ct.is_contiguous() and ct.device == self.ctx.device):
+            raise ValueError("plane_map: `ct` must be a contiguous int64 tensor [..., n_in, size, k, n] = [..., %d, size, %d, %d] on the context's device, got %r"
+                             % ((plan.n_in,) + kn + (tuple(getattr(ct, "shape", ())),)))
+        shape = tuple(ct.shape[:-4]) + (plan.n_out,) + tuple(ct.shape[-3:])
+        if out is not None and (tuple(out.shape) != shape or out.dtype != ct.dtype or not out.is_contiguous() or out.device != ct.device):
+            raise ValueError("plane_map: `out` must be a contiguous int64 tensor %r on the input's device, got %r" % (shape, tuple(out.shape)))
+        out = torch.empty(shape, dtype=torch.int64, device=ct.device) if out is None else out
+        size = int(ct.shape[-3])
+        count = ct.numel() // (plan.n_in * size * kn[0] * kn[1])
+        _lib.call("fhe_plane_map", self.ctx.h, plan.h, _ptr(ct), _ptr(out), size, count, _stream())
         return out
 
     # -- primitives named by the north star ---------------------------------------------------------

@@ -11,6 +11,8 @@
 //                                resize_bicubic (shared offsets), homomorphic_sin / _cos, approximated_step, decode_channel
 //   seal::hip::Block8x8Plan,     integer linear maps across slot-packed ciphertexts on a CiphertextBatch (include/fhe_hip.h: the packed JPEG
 //   block8x8_scalar, channel_mix transform): groups of 64 ciphertexts packed by block position, planes of a colour conversion; dct8_matrix
+//   seal::hip::PlaneMapPlan,     sparse integer maps across position-packed ciphertexts (fhe_plane_map): packed resize, tile filters
+//   plane_map
 //
 // (The slot encoder and the Galois rotations -- seal::hip::batch_encode / batch_decode, GaloisKeys, generate_galois_keys, apply_galois,
 // rotate_rows, rotate_columns -- work on std::vector<seal::Ciphertext> and live in seal/seal.h, beside filter2d and remap.)
@@ -431,6 +433,47 @@ inline CiphertextBatch channel_mix(const SEALContext &ctx, const std::vector<int
     const uint64_t ctw = planes.ct_words();
     detail::check(fhe_channel_mix(ctx.state()->h, M.data(), bias.empty() ? nullptr : bias.data(), c, m, planes.ptr(), ctw, per * ctw, out.ptr(), ctw, per * ctw, planes.size(),
                                   per, nullptr), "channel_mix");
+    return out;
+}
+
+// ---- sparse integer maps across position-packed ciphertexts (include/fhe_hip.h: fhe_plane_map) -----------------------------------------
+// what PlaneMapPlan / Evaluator.plane_map are to the Python host: taps, weights [n_out][T] row-major, order empty = index order
+class PlaneMapPlan {
+public:
+    PlaneMapPlan(const SEALContext &ctx, uint32_t n_in, uint32_t T, const std::vector<uint32_t> &taps, const std::vector<int64_t> &weights,
+                 const std::vector<uint32_t> &order = std::vector<uint32_t>(), uint32_t window = 0)
+        : ctx_(ctx), h_(nullptr), n_in_(n_in), n_out_(0), groups_(0), window_(0), source_reads_(0) {
+        if (!T || taps.empty() || taps.size() % T || weights.size() != taps.size() || (!order.empty() && order.size() != taps.size() / T))
+            throw std::invalid_argument("PlaneMapPlan: taps and weights are [n_out][T], order has n_out entries or none");
+        n_out_ = (uint32_t)(taps.size() / T);
+        detail::check(fhe_plane_map_plan_create(ctx.state()->h, n_in, n_out_, T, taps.data(), weights.data(), order.empty() ? nullptr : order.data(), window, nullptr, &h_),
+                      "plane_map_plan_create");
+        fhe_plane_map_plan_info(h_, &groups_, &source_reads_, &window_);
+    }
+    ~PlaneMapPlan() { if (h_) fhe_plane_map_plan_destroy(h_); }
+    PlaneMapPlan(const PlaneMapPlan &) = delete;
+    PlaneMapPlan &operator=(const PlaneMapPlan &) = delete;
+    const fhe_plane_map_plan *handle() const { return h_; }
+    const SEALContext &context() const { return ctx_; }
+    uint32_t n_in() const { return n_in_; }
+    uint32_t n_out() const { return n_out_; }
+    uint32_t groups() const { return groups_; }
+    uint32_t window() const { return window_; }
+    uint64_t source_reads() const { return source_reads_; }
+private:
+    SEALContext ctx_;
+    fhe_plane_map_plan *h_;
+    uint32_t n_in_, n_out_, groups_, window_;
+    uint64_t source_reads_;
+};
+
+// frames of n_in ciphertexts: batch [frames * n_in][size][k][n] -> [frames * n_out][size][k][n]
+inline CiphertextBatch plane_map(const PlaneMapPlan &plan, const CiphertextBatch &frames) {
+    if (frames.count() % plan.n_in()) throw std::invalid_argument("plane_map: the batch must hold whole frames of n_in ciphertexts");
+    if (!frames.of(plan.context())) throw std::invalid_argument("plane_map: the batch does not belong to the plan's context");
+    const size_t count = frames.count() / plan.n_in();
+    CiphertextBatch out(plan.context(), count * plan.n_out(), frames.size());
+    detail::check(fhe_plane_map(plan.context().state()->h, plan.handle(), frames.ptr(), out.ptr(), frames.size(), count, nullptr), "plane_map");
     return out;
 }
 

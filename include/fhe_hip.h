@@ -82,7 +82,8 @@ const char *fhe_last_error(void);
  *      new entry points only, no existing signature or contract changed.  The same holds for the fhe_filter_* entry points (2-D convolution)
  *      and for fhe_weight_table_*, fhe_remap* and fhe_resample_axis_plan (resampling with public weights), and for fhe_batch_encode /
  *      fhe_batch_decode, fhe_galois_element and fhe_apply_galois (batched slots and Galois rotations), and for fhe_block8x8_plan_create /
- *      destroy, fhe_block8x8_scalar, fhe_channel_mix and fhe_dct8_matrix (integer linear maps across slot-packed ciphertexts).
+ *      destroy, fhe_block8x8_scalar, fhe_channel_mix and fhe_dct8_matrix (integer linear maps across slot-packed ciphertexts), and for
+ *      fhe_plane_map_plan_create / destroy / info and fhe_plane_map (sparse integer maps across position-packed ciphertexts).
  * A host compiled against this header compares fhe_abi_version() with FHE_ABI_VERSION before anything else (the Python
  * binding and seal/seal.h do). */
 #define FHE_ABI_VERSION 4
@@ -361,6 +362,44 @@ int fhe_channel_mix(const fhe_ctx *ctx, const int64_t *M, const int64_t *bias, u
  * transform of its own: its ciphertexts and decrypted values are NOT those of fhe_dct8x8_quant below, which follows the reference's
  * FractionalEncoder circuit. */
 int fhe_dct8_matrix(int bits, int64_t *D);
+
+/* ---- sparse integer maps across position-packed ciphertexts: packed resize, warps, tile filters -------------------------------------
+ * A client that packs by POSITION -- ciphertext p of a frame of n_in ciphertexts holds, in slot b, pixel p of frame (or tile) b -- turns a
+ * resize, a warp, a strided filter or a chroma subsampling into one sparse linear map across ciphertexts with integer scalar weights (the
+ * scalar rule above): no transform, no rotation, no key.  New entry points only.
+ *
+ * fhe_plane_map: in [count][n_in][size][k][n], out [count][n_out][size][k][n].  For output plane o, visiting slots p = 0 .. T - 1 in order:
+ * a slot of weight 0 is skipped (its tap is not looked at); otherwise the term is multiply_plain(in[taps[o][p]], [weights[o][p] mod t]); the
+ * terms are combined with add.  The result has `size` polynomials, is fully reduced and is bit-identical to that composition (exact ring
+ * operations: any order of evaluation gives the same bits).  A source may appear twice in one output: two terms.
+ *
+ * fhe_plane_map_plan_create refuses (FHE_ERR_PARAM): an output with no live term (the transparent zero), a live tap >= n_in, T outside
+ * 1 .. FHE_PLANE_MAX_TAPS, n_in or n_out of 0 or above FHE_PLANE_MAX_PLANES, a window other than 0, 16, 32, 64, an order that is not a
+ * permutation of 0 .. n_out - 1, a scalar out of range, a null pointer (order may be NULL: index order).  fhe_plane_map refuses size < 2,
+ * size > FHE_MAX_POLYS, a null pointer, a plan of another context and an output range that overlaps the input range in any way (the plane
+ * counts differ: there is no in-place form) -- all before anything is enqueued.  count == 0 is a no-op.  No scratch.
+ *
+ * Groups.  The plan cuts the outputs into groups; the kernel loads the distinct live sources of a group once (at most 64 words per thread,
+ * in LDS) and forms the group's outputs from them (csrc/planemap.hip).  The cut is made in plan_create and is the same on every host: walk
+ * the outputs in `order` (index order when NULL); an output joins the open group while the union of the group's live sources stays <=
+ * window, otherwise the group is closed and the output opens the next one.  An output with more live sources than the window (at most 64:
+ * T <= 64) still gets a group of its own -- the window is raised to 64 for that group.  window 0 = the library's default, 16
+ * (FHE_PLANEMAP_WINDOW in the environment of fhe_ctx_create overrides it).  The bits do not depend on the cut.  fhe_plane_map_plan_info
+ * reports the number of groups, source_reads = the sum over groups of their distinct sources (read amplification = source_reads / distinct
+ * sources used) and the window of the cut; any of the three pointers may be NULL.  The plan keeps its tables on the device and belongs to
+ * its context.
+ * Which kernel runs.  A plan created with window 0 runs the direct kernel (one thread per output word, sources from global memory, the
+ * groups unused): it measured faster than the windowed one in two of six cases.  A plan created with an explicit window, and every plan of
+ * a context created with FHE_PLANEMAP_WINDOW=16|32|64, runs the windowed kernel; FHE_PLANEMAP_DIRECT=1 forces the direct one.  Same bits. */
+#define FHE_PLANE_MAX_TAPS 64
+#define FHE_PLANE_MAX_PLANES 65536
+typedef struct fhe_plane_map_plan fhe_plane_map_plan;
+int fhe_plane_map_plan_create(const fhe_ctx *ctx, uint32_t n_in, uint32_t n_out, uint32_t T, const uint32_t *taps, const int64_t *weights,
+                              const uint32_t *order, uint32_t window, fhe_stream stream, fhe_plane_map_plan **out);
+int fhe_plane_map_plan_destroy(fhe_plane_map_plan *plan);
+int fhe_plane_map_plan_info(const fhe_plane_map_plan *plan, uint32_t *groups, uint64_t *source_reads, uint32_t *window);
+int fhe_plane_map(const fhe_ctx *ctx, const fhe_plane_map_plan *plan, const uint64_t *in, uint64_t *out, uint32_t size, uint64_t count,
+                  fhe_stream stream);
 
 /* ---- fused block circuit: encrypted_dct (homo/fhe_image.h:196-288) followed by quantize_fhe
  * (homo/fhe_image.h:294-305) on n_blocks independent 8x8 blocks.  in/out: [n_blocks][64][2][k][n].
