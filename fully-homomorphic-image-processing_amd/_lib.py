@@ -30,6 +30,7 @@ SIGNATURES = {
     "fhe_last_error": (C.c_char_p, []),
     "fhe_abi_version": (_u32, []),
     "fhe_ctx_create": (_i, [_u32, C.POINTER(_u64), _u32, _u64, _i, C.POINTER(_vp)]),
+    "fhe_ctx_create_level": (_i, [_vp, _u32, C.POINTER(_vp)]),
     "fhe_ctx_destroy": (_i, [_vp]),
     "fhe_ctx_has_ctct_tables": (_i, [_vp]),
     "fhe_ctx_device": (_i, [_vp]),
@@ -96,6 +97,7 @@ SIGNATURES = {
     "fhe_plane_map_plan_destroy": (_i, [_vp]),
     "fhe_plane_map_plan_info": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u64), C.POINTER(_u32)]),
     "fhe_plane_map": (_i, [_vp, _vp, _vp, _vp, _u32, _u64, _vp]),
+    "fhe_mod_switch": (_i, [_vp, _u32, _vp, _vp, _u64, _vp]),
     "fhe_dct_plan_create": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(_vp)]),
     "fhe_dct_plan_destroy": (_i, [_vp]),
     "fhe_dct8x8_scratch_bytes": (_sz, [_vp, _u64]),

@@ -851,3 +851,31 @@ def packed_tile_resize_plans(src_w, src_h, dst_w, dst_h, core_w, core_h, kernel=
     ty, wy, hy, oh = _tile_axis(src_h, dst_h, core_h, kernel, antialias, convention, weight_bits)
     h, v = _resize_pair(ctx, tx, wx, ty, wy, core_w + 2 * hx, core_h + 2 * hy, int(weight_bits), window)
     return h, v, (hx, hy), (ow, oh)
+
+
+# -- modulus switching (Evaluator.mod_switch): how much budget a switch keeps, how far a result can be switched ------------------------------
+def mod_switch_budget(ctx, budget_bits, k_out, size=2):
+    """Lower bound (bits, float) on the invariant noise budget of a ciphertext of `size` polynomials under a ternary secret after
+    mod_switch to k_out primes, from its budget before.  One drop to the base q' adds at most t S / (2 q') to the invariant noise
+    ||v|| = 2^(-B-1), S = 1 + n + .. + n^(size-1) (the rounding error of each polynomial, at most 1/2 per coefficient, times the power of
+    the secret it multiplies), so
+        B_after >= -log2(2^-B + sum over the bases q' = q_0 .. q_(j-1), j = k - 1 .. k_out, of t S / q').
+    Pure Python on ctx.n, ctx.t, ctx.q: `ctx` may be any object with those attributes."""
+    from fractions import Fraction
+    q, k, k_out = [int(x) for x in ctx.q], len(ctx.q), int(k_out)
+    if not 1 <= k_out <= k:
+        raise ValueError("mod_switch_budget: k_out = %d of %d primes" % (k_out, k))
+    S = sum(int(ctx.n) ** j for j in range(int(size)))
+    total = Fraction(1, 1 << int(budget_bits)) if float(budget_bits) == int(budget_bits) else Fraction(2.0 ** -float(budget_bits))
+    for j in range(k - 1, k_out - 1, -1):
+        total += Fraction(int(ctx.t) * S, math.prod(q[:j]))
+    return math.log2(total.denominator) - math.log2(total.numerator)
+
+
+def mod_switch_primes(ctx, budget_bits, keep_bits, size=2):
+    """The smallest k_out whose mod_switch_budget is at least keep_bits; ctx.k (no switch) when not even one drop qualifies."""
+    k = len(ctx.q)
+    for k_out in range(1, k):
+        if mod_switch_budget(ctx, budget_bits, k_out, size) >= keep_bits:
+            return k_out
+    return k

@@ -209,7 +209,8 @@ extern "C" int fhe_default_coeff_modulus(uint32_t n, int preset, uint64_t *q_out
     return cnt;
 }
 
-extern "C" int fhe_ctx_create(uint32_t n, const uint64_t *q, uint32_t k, uint64_t t, int device, fhe_ctx **out) {
+// inherit: the switches of a parent context (fhe_ctx_create_level) instead of the environment's
+static int ctx_create(uint32_t n, const uint64_t *q, uint32_t k, uint64_t t, int device, const FheOptions *inherit, fhe_ctx **out) {
     using namespace hostmath;
     if (!out || !q) return fail(FHE_ERR_PARAM, "null argument");
     *out = nullptr;
@@ -231,7 +232,8 @@ extern "C" int fhe_ctx_create(uint32_t n, const uint64_t *q, uint32_t k, uint64_
             if (primes[j] == primes[i]) return fail(FHE_ERR_PARAM, "duplicate modulus");
     }
     fhe_ctx *c = new fhe_ctx();
-    {   // the experiment switches, once (internal.h: FheOptions)
+    if (inherit) c->opt = *inherit;
+    else {   // the experiment switches, once (internal.h: FheOptions)
         FheOptions &o = c->opt;
         auto off = [](const char *name) { const char *e = getenv(name); return e && e[0] == '0' && !e[1]; };
         o.force_u64 = env_on("FHE_DCT_FORCE_U64");
@@ -271,6 +273,7 @@ extern "C" int fhe_ctx_create(uint32_t n, const uint64_t *q, uint32_t k, uint64_
     for (u32 i = 0; i < k; ++i) c->max_prime_bits = std::max(c->max_prime_bits, bit_length(primes[i]));
     int rc = fhe_build_base(c->qb, primes, n, c->logn, c->max_prime_bits <= 47);
     if (rc) { delete c; return rc; }
+    fhe_modswitch_build(c);
     // plaintext lifting constants
     BigUInt Q(1);
     for (u32 i = 0; i < k; ++i) Q.mul_small(primes[i]);
@@ -300,6 +303,17 @@ extern "C" int fhe_ctx_create(uint32_t n, const uint64_t *q, uint32_t k, uint64_
     if (!ok) { fhe_ctx_destroy(c); return fail(FHE_ERR_HIP, "stream/event creation failed"); }
     *out = c;
     return FHE_OK;
+}
+
+extern "C" int fhe_ctx_create(uint32_t n, const uint64_t *q, uint32_t k, uint64_t t, int device, fhe_ctx **out) {
+    return ctx_create(n, q, k, t, device, nullptr, out);
+}
+// a context of its own (tables, lifting constants, streams) over the parent's first k_out primes: what a fhe_mod_switch result lives in
+extern "C" int fhe_ctx_create_level(const fhe_ctx *parent, uint32_t k_out, fhe_ctx **out) {
+    if (!parent || !out) return fail(FHE_ERR_PARAM, "null argument");
+    *out = nullptr;
+    if (k_out == 0 || k_out >= parent->k) return fail(FHE_ERR_PARAM, "level context: k_out = %u, a context of %u primes has levels 1 .. %u", k_out, parent->k, parent->k - 1);
+    return ctx_create(parent->n, (const uint64_t *)parent->qb.primes.data(), k_out, parent->t, parent->device, &parent->opt, out);
 }
 
 extern "C" int fhe_ctx_destroy(fhe_ctx *c) {

@@ -77,6 +77,14 @@ struct FheOptions {
                                      // product, 5 % slower -- the y_i are recomputed per auxiliary prime and the kernels are issue-bound; profiles/EXPERIMENTS.md)
 };
 
+// fhe_mod_switch (modswitch.hip): per pair (dropped q_m, kept q_i), entry m (m - 1) / 2 + i: p^-1 mod q_i with its Shoup companion, and
+// (floor(p / 2) mod q_i) + the smallest multiple of q_i that is >= p.  Built on the host in fhe_ctx_create, handed to the kernel by value.
+struct ModSwitchTab {
+    u64 q[FHE_MAX_K];
+    ulonglong2 inv[FHE_MAX_K * (FHE_MAX_K - 1) / 2];
+    u64 add[FHE_MAX_K * (FHE_MAX_K - 1) / 2];
+};
+
 struct fhe_ctx {
     u32 n = 0, logn = 0, k = 0;
     FheOptions opt;
@@ -84,6 +92,7 @@ struct fhe_ctx {
     int device = 0;
     int max_prime_bits = 0;
     BaseTables qb;     // q-base
+    ModSwitchTab modswitch{};
     // plaintext lifting (SEAL 2.3 multiply_plain / preencrypt semantics)
     u64 upper_half_threshold = 0;
     u64 plain_upper_half_increment[FHE_MAX_K] = {0};   // (q - t) mod q_i
@@ -177,6 +186,7 @@ int fhe_stage_release(const FheStage &sg, hipStream_t st);
 int fhe_ntt_launch(bool inverse, const fhe_ctx *c, const BaseTables &B, const u64 *in, u64 *out, u64 n_res_polys, hipStream_t st);
 int fhe_build_base(BaseTables &B, const std::vector<u64> &primes, u32 n, u32 logn, bool want_f64);
 void fhe_free_base(BaseTables &B);
+void fhe_modswitch_build(fhe_ctx *c);   // modswitch.hip; host arithmetic only
 int fhe_behz_build(fhe_ctx *c);   // called once per context, through fhe_behz_ensure
 int fhe_behz_ensure(const fhe_ctx *c);
 // Cubic's three products with their tail fused into the floor / back conversion (behz.hip: k_behz_floor3_combine_pm).

@@ -90,6 +90,19 @@ class SEALContext:
         p = PRESETS[name]
         return cls(p["n"], p["q"], p["t"], device, switches)
 
+    def level(self, k_out):
+        """The context a mod_switch result lives in (fhe_ctx_create_level): this context's n, t, device and switches over its first k_out
+        primes.  Created on first use and kept for the life of this context; Decryptor(ctx.level(k_out), sk[:k_out]) decrypts there."""
+        k_out = int(k_out)
+        levels = self.__dict__.setdefault("_levels", {})
+        if k_out not in levels:
+            h = C.c_void_p()
+            _lib.call("fhe_ctx_create_level", self.h, k_out, C.byref(h))
+            child = object.__new__(SEALContext)
+            child.n, child.q, child.t, child.k, child.device, child.h = self.n, self.q[:k_out], self.t, k_out, self.device, h
+            levels[k_out] = child
+        return levels[k_out]
+
     def __del__(self):
         h = getattr(self, "h", None)
         if h:
@@ -714,6 +727,24 @@ class Evaluator:
         size = int(ct.shape[-3])
         count = ct.numel() // (plan.n_in * size * kn[0] * kn[1])
         _lib.call("fhe_plane_map", self.ctx.h, plan.h, _ptr(ct), _ptr(out), size, count, _stream())
+        return out
+
+    def mod_switch(self, ct, k_out, out=None):
+        """Modulus switching (fhe_mod_switch): ct [..., size, k, n] -> [..., size, k_out, n], every polynomial scaled and rounded from this
+        context's k primes to its first k_out, one dropped prime after the other, last first.  The result belongs to ctx.level(k_out) and
+        decrypts there under sk[:k_out] to the same plaintext; circuits.mod_switch_budget bounds the budget it keeps.  `out` may not overlap `ct`."""
+        k, n, k_out = self.ctx.k, self.ctx.n, int(k_out)
+        if not (isinstance(ct, torch.Tensor) and ct.dim() >= 3 and tuple(ct.shape[-2:]) == (k, n) and ct.dtype == torch.int64 and ct.is_contiguous()
+                and ct.device == self.ctx.device):
+            raise ValueError("mod_switch: `ct` must be a contiguous int64 tensor [..., size, k, n] = [..., size, %d, %d] on the context's device, got %r"
+                             % (k, n, tuple(getattr(ct, "shape", ()))))
+        if not 1 <= k_out < k:
+            raise ValueError("mod_switch: k_out = %d, a context of %d primes switches to 1 .. %d" % (k_out, k, k - 1))
+        shape = tuple(ct.shape[:-2]) + (k_out, n)
+        if out is not None and (tuple(out.shape) != shape or out.dtype != ct.dtype or not out.is_contiguous() or out.device != ct.device):
+            raise ValueError("mod_switch: `out` must be a contiguous int64 tensor %r on the input's device, got %r" % (shape, tuple(out.shape)))
+        out = torch.empty(shape, dtype=torch.int64, device=ct.device) if out is None else out
+        _lib.call("fhe_mod_switch", self.ctx.h, k_out, _ptr(ct), _ptr(out), ct.numel() // (k * n), _stream())
         return out
 
     # -- primitives named by the north star ---------------------------------------------------------

@@ -96,10 +96,16 @@ def _ring_mul(ctx, a, b_ntt):
 
 
 class KeyGenerator:
-    def __init__(self, ctx, seed=None):
+    def __init__(self, ctx, seed=None, secret_key=None):
+        """secret_key: an existing key ([k, n] coefficient residues on the context's device) instead of a fresh one -- public, evaluation
+        and Galois keys are then generated for THAT key on this context.  With a level context (SEALContext.level) pass sk[:k_out]."""
         self.ctx = ctx
         smp = _Sampler(ctx, seed)
-        self._sk = to_device(smp.ternary()[None], ctx.device)               # [1, k, n]
+        if secret_key is None:
+            self._sk = to_device(smp.ternary()[None], ctx.device)           # [1, k, n]
+        else:
+            _check_key(ctx, secret_key, 1, "KeyGenerator: secret key")
+            self._sk = secret_key[None].contiguous().clone()
         self._sk_ntt = _ntt(ctx, self._sk)[0]
         a = to_device(smp.uniform()[None], ctx.device)
         e = to_device(smp.noise()[None], ctx.device)

@@ -13,6 +13,8 @@
 //   block8x8_scalar, channel_mix transform): groups of 64 ciphertexts packed by block position, planes of a colour conversion; dct8_matrix
 //   seal::hip::PlaneMapPlan,     sparse integer maps across position-packed ciphertexts (fhe_plane_map): packed resize, tile filters
 //   plane_map
+//   seal::hip::level_context,    modulus switching (fhe_mod_switch): a batch goes from the context's k primes to its first k_out, into the
+//   mod_switch                   level context, where it decrypts under the same secret key restricted to those primes
 //
 // (The slot encoder and the Galois rotations -- seal::hip::batch_encode / batch_decode, GaloisKeys, generate_galois_keys, apply_galois,
 // rotate_rows, rotate_columns -- work on std::vector<seal::Ciphertext> and live in seal/seal.h, beside filter2d and remap.)
@@ -474,6 +476,22 @@ inline CiphertextBatch plane_map(const PlaneMapPlan &plan, const CiphertextBatch
     const size_t count = frames.count() / plan.n_in();
     CiphertextBatch out(plan.context(), count * plan.n_out(), frames.size());
     detail::check(fhe_plane_map(plan.context().state()->h, plan.handle(), frames.ptr(), out.ptr(), frames.size(), count, nullptr), "plane_map");
+    return out;
+}
+
+// ---- modulus switching (include/fhe_hip.h: fhe_mod_switch) ---------------------------------------------------------------------------
+// what SEALContext.level / Evaluator.mod_switch are to the Python host.  The level context is a context of its own; keep it as long as its
+// batches are used.
+inline SEALContext level_context(const SEALContext &ctx, uint32_t k_out) { return SEALContext(ctx, k_out); }
+
+// [count][size][k][n] of `ctx` -> [count][size][k_out][n] of `level` (= level_context(ctx, k_out)): one kernel
+inline CiphertextBatch mod_switch(const SEALContext &ctx, const SEALContext &level, const CiphertextBatch &in) {
+    const detail::CtxState &s = *ctx.state(), &l = *level.state();
+    if (!in.of(ctx)) throw std::invalid_argument("mod_switch: the batch does not belong to the context");
+    if (l.n != s.n || l.t != s.t || l.k >= s.k || !std::equal(l.q.begin(), l.q.end(), s.q.begin()))
+        throw std::invalid_argument("mod_switch: `level` is not a level context of `ctx`");
+    CiphertextBatch out(level, in.count(), in.size());
+    detail::check(fhe_mod_switch(s.h, l.k, in.ptr(), out.ptr(), (uint64_t)in.count() * in.size(), nullptr), "mod_switch");
     return out;
 }
 

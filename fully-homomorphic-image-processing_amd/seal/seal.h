@@ -360,15 +360,22 @@ public:
         const double tc = detail::now_s();
         detail::check(fhe_ctx_create(s.n, s.q.data(), s.k, s.t, dev, &s.h), "SEALContext");
         s.stats.create_s = detail::now_s() - tc;
-        s.Q = detail::Big(1);
-        for (uint64_t qi : s.q) s.Q.mul_small(qi);
-        total_ = BigUInt(s.Q.bits());
-        {
-            std::lock_guard<std::mutex> lk(detail::known_moduli_mu());
-            bool known = false;
-            for (const auto &m : detail::known_moduli_unlocked()) known |= (m.k == s.k && m.n == s.n && m.q == s.q);
-            if (!known) detail::known_moduli_unlocked().push_back(detail::KnownModuli{s.k, s.n, s.q});
-        }
+        finish();
+    }
+    // the level context of `parent` (fhe_ctx_create_level): its n, t, device and switches over its first k_out primes -- where the results of
+    // seal::hip::mod_switch live (seal/hip_circuits.h: level_context)
+    SEALContext(const SEALContext &parent, uint32_t k_out) : st_(std::make_shared<detail::CtxState>()), poly_(parent.poly_), plain_(parent.plain_) {
+        const detail::CtxState &ps = *parent.st_;
+        if (k_out == 0 || k_out >= ps.k) throw std::invalid_argument("level context: 1 <= k_out < the parent's number of primes");
+        detail::CtxState &s = *st_;
+        s.n = ps.n;
+        s.k = k_out;
+        s.t = ps.t;
+        s.q.assign(ps.q.begin(), ps.q.begin() + k_out);
+        const double tc = detail::now_s();
+        detail::check(fhe_ctx_create_level(ps.h, k_out, &s.h), "SEALContext (level)");
+        s.stats.create_s = detail::now_s() - tc;
+        finish();
     }
     const SmallModulus &plain_modulus() const { return plain_; }
     const BigPoly &poly_modulus() const { return poly_; }
@@ -376,6 +383,16 @@ public:
     double noise_standard_deviation() const { return 3.19; }
     const std::shared_ptr<detail::CtxState> &state() const { return st_; }
 private:
+    void finish() {
+        detail::CtxState &s = *st_;
+        s.Q = detail::Big(1);
+        for (uint64_t qi : s.q) s.Q.mul_small(qi);
+        total_ = BigUInt(s.Q.bits());
+        std::lock_guard<std::mutex> lk(detail::known_moduli_mu());
+        bool known = false;
+        for (const auto &m : detail::known_moduli_unlocked()) known |= (m.k == s.k && m.n == s.n && m.q == s.q);
+        if (!known) detail::known_moduli_unlocked().push_back(detail::KnownModuli{s.k, s.n, s.q});
+    }
     std::shared_ptr<detail::CtxState> st_;
     BigPoly poly_;
     SmallModulus plain_;

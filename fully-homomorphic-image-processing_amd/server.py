@@ -145,6 +145,17 @@ class StreamFile:
             self.h = None
 
 
+def _out_level(ctx, out_primes):
+    """out_primes=None: (ctx, None) -- nothing changes.  Otherwise the level context the output records belong to and its number of primes:
+    each output wave is mod-switched on the device (Evaluator.mod_switch) before its download and written with k = out_primes."""
+    if out_primes is None:
+        return ctx, None
+    out_primes = int(out_primes)
+    if not 1 <= out_primes < ctx.k:
+        raise ValueError("out_primes = %d: a context of %d primes switches its output to 1 .. %d" % (out_primes, ctx.k, ctx.k - 1))
+    return ctx.level(out_primes), out_primes
+
+
 class _ResidueCheck:
     """fhe_count_unreduced on every uploaded wave: the streams' record headers are checked by the I/O layer, the payload here --
     a residue at or above its modulus would otherwise be computed on silently (seal::Ciphertext::load rejects it, and so does
@@ -216,7 +227,7 @@ def _stop_pipeline(reader_thread, writer_thread, free_in, to_write):
     torch.cuda.synchronize()
 
 
-def server_jpeg(ctx, in_path, out_path, n_blocks, wave_blocks=8, quant=None, do_dct=True, io_threads=8, slots=3, stats=None, validate=True):
+def server_jpeg(ctx, in_path, out_path, n_blocks, wave_blocks=8, quant=None, do_dct=True, io_threads=8, slots=3, stats=None, validate=True, out_primes=None):
     """Process `n_blocks` colour blocks.  in_path / out_path: file names, or StreamFile objects a long-lived server keeps
     open (their mappings, and the page-table entries behind them, are then reused from call to call).  Input order per block: 64 R, 64 G, 64 B ciphertexts
     (homo/server_jpeg.cpp:115-124).  Output order per block: 64 Y, 64 Cb, 64 Cr
@@ -234,7 +245,9 @@ def server_jpeg(ctx, in_path, out_path, n_blocks, wave_blocks=8, quant=None, do_
     Events order the hand-overs; the host never waits for the device except where a buffer is about to be reused.
     stats (a dict), if given, receives wall seconds, device compute seconds and byte counts.
     validate: every uploaded wave is checked for residues that are not below their modulus (fhe_count_unreduced; ValueError at
-    the end of the job -- what Ciphertext::load rejects per ciphertext, homo/server_jpeg.cpp:117-123)."""
+    the end of the job -- what Ciphertext::load rejects per ciphertext, homo/server_jpeg.cpp:117-123).
+    out_primes: None, or the number of primes the output records keep (1 .. k - 1): every output wave is mod-switched on the device before
+    its download, the records carry k = out_primes and belong to ctx.level(out_primes) -- the client decrypts there with sk[:out_primes]."""
     ev = Evaluator(ctx)
     plan = DctPlan(ctx, quant) if do_dct else None
 
@@ -243,15 +256,17 @@ def server_jpeg(ctx, in_path, out_path, n_blocks, wave_blocks=8, quant=None, do_
         if do_dct:
             ev.dct8x8_quant(plan, din.view(nb * 3, 64, 2, ctx.k, ctx.n), out=dout.view(nb * 3, 64, 2, ctx.k, ctx.n))
 
-    return _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, do_dct, io_threads, slots, stats, validate)
+    return _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, do_dct, io_threads, slots, stats, validate, out_primes)
 
 
-def server_jpeg_decompress(ctx, in_path, out_path, n_blocks, quant=None, to_rgb=True, wave_blocks=8, io_threads=8, slots=3, stats=None, validate=True):
+def server_jpeg_decompress(ctx, in_path, out_path, n_blocks, quant=None, to_rgb=True, wave_blocks=8, io_threads=8, slots=3, stats=None, validate=True,
+                           out_primes=None):
     """The way back: reads what server_jpeg writes (per block 64 Y, 64 Cb, 64 Cr ciphertexts of quantised DCT coefficients) and
     writes what server_jpeg reads (per block 64 R, 64 G, 64 B).  Per wave: fhe_idct8x8_dequant over the 3 * wave channel-blocks
     (dequantisation by `quant`, None: skipped -- pass the table server_jpeg quantised with), then, with to_rgb, fhe_ycc_to_rgb_blocks in
     place on the stream layout.  Same five-stage pipeline, arguments and residue validation as server_jpeg.  Returns blocks processed.
-    A server_jpeg + server_jpeg_decompress round trip decrypts to the pixels only with a plain modulus t >= 2^26 (include/fhe_hip.h)."""
+    A server_jpeg + server_jpeg_decompress round trip decrypts to the pixels only with a plain modulus t >= 2^26 (include/fhe_hip.h).
+    out_primes: as server_jpeg's."""
     ev = Evaluator(ctx)
     plan = IdctPlan(ctx, quant)
 
@@ -260,12 +275,13 @@ def server_jpeg_decompress(ctx, in_path, out_path, n_blocks, quant=None, to_rgb=
         if to_rgb:
             ev.ycc_to_rgb_blocks(dout)                           # in place: R, G, B in the stream's block layout
 
-    return _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, True, io_threads, slots, stats, validate)
+    return _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, True, io_threads, slots, stats, validate, out_primes)
 
 
-def _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, separate_out, io_threads, slots, stats, validate):
+def _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, separate_out, io_threads, slots, stats, validate, out_primes=None):
     """server_jpeg's pipeline over records of 192 ciphertexts per block; compute(din, dout, nb) runs on the main stream for one wave
-    (din is dout unless separate_out)."""
+    (din is dout unless separate_out).  out_primes: the wave's result is mod-switched into a buffer of the level context's shape, which is
+    what the download, the output staging buffers and the writer see."""
     import queue
     import threading
     import time
@@ -274,19 +290,24 @@ def _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, separa
     slots = max(2, slots)
     shape = (wave_blocks, 3, 64, 2, ctx.k, ctx.n)            # wave: block, channel, pixel, poly, prime, coeff
     hin = [_pinned(("in", i), shape) for i in range(slots)]
-    hout = [_pinned(("out", i), shape) for i in range(slots)]
+    octx, out_primes = _out_level(ctx, out_primes)
+    oshape = (wave_blocks, 3, 64, 2, octx.k, octx.n)
+    hout = [_pinned(("out", i), oshape) for i in range(slots)]
     din = [torch.empty(shape, dtype=torch.int64, device=ctx.device) for _ in range(2)]
     dout = [torch.empty(shape, dtype=torch.int64, device=ctx.device) for _ in range(2)] if separate_out else din
+    dlow = [torch.empty(oshape, dtype=torch.int64, device=ctx.device) for _ in range(2)] if out_primes else dout      # what leaves for the host
+    switcher = Evaluator(ctx) if out_primes else None
     main = torch.cuda.current_stream()
     h2d, d2h = _copy_streams()
     rec = RECORD_HEADER + 2 * ctx.k * ctx.n * 8
+    rec_out = RECORD_HEADER + 2 * octx.k * octx.n * 8
     if (in_path.size if isinstance(in_path, StreamFile) else os.path.getsize(in_path)) < n_blocks * 192 * rec:
         raise EOFError("ciphertext stream ended")
     waves = [(s, min(s + wave_blocks, n_blocks)) for s in range(0, n_blocks, wave_blocks)]
     own_in, own_out = not isinstance(in_path, StreamFile), not isinstance(out_path, StreamFile)
     fin = StreamFile(in_path) if own_in else in_path
-    fout = StreamFile(out_path, write=True, size=n_blocks * 192 * rec) if own_out else out_path
-    if fout.size < n_blocks * 192 * rec:
+    fout = StreamFile(out_path, write=True, size=n_blocks * 192 * rec_out) if own_out else out_path
+    if fout.size < n_blocks * 192 * rec_out:
         raise ValueError("output stream file is smaller than the result")
     trace = [] if stats is not None else None
     free_in, ready_in, free_out, to_write = queue.Queue(), queue.Queue(), queue.Queue(), queue.Queue()
@@ -324,7 +345,7 @@ def _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, separa
                 (s, e), slot, landed = item
                 landed.synchronize()
                 t_io = time.perf_counter()
-                fout.transfer(s * 192, (e - s) * 192, 2, ctx, hout[slot], io_threads)
+                fout.transfer(s * 192, (e - s) * 192, 2, octx, hout[slot], io_threads)
                 io_seconds["write"] += time.perf_counter() - t_io
                 if trace is not None:
                     trace.append(("write", s // wave_blocks, t_io - t0, time.perf_counter() - t0))
@@ -370,6 +391,8 @@ def _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, separa
                 t_start[-1].record(main)
             residues.add(din[d][:nb])
             compute(din[d][:nb], dout[d][:nb], nb)
+            if out_primes:
+                switcher.mod_switch(dout[d][:nb], out_primes, out=dlow[d][:nb])
             if stats is not None:
                 t_stop.append(torch.cuda.Event(enable_timing=True))
                 t_stop[-1].record(main)
@@ -386,7 +409,7 @@ def _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, separa
                 trace.append(("main", wi, t_w - t0, time.perf_counter() - t0))
             with torch.cuda.stream(d2h):
                 d2h.wait_event(done)
-                hout[oslot][:nb].copy_(dout[d][:nb], non_blocking=True)
+                hout[oslot][:nb].copy_(dlow[d][:nb], non_blocking=True)
                 landed = torch.cuda.Event()
                 landed.record(d2h)
             drained[d] = landed
@@ -400,7 +423,7 @@ def _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, separa
         residues.verdict(_refuser(own_out, fout, out_path))
         if stats is not None:
             stats.update(seconds=time.perf_counter() - t0, device_compute_seconds=sum(a.elapsed_time(b) for a, b in zip(t_start, t_stop)) / 1e3,
-                         bytes_in=n_blocks * 192 * rec, bytes_out=n_blocks * 192 * rec, waves=len(waves),
+                         bytes_in=n_blocks * 192 * rec, bytes_out=n_blocks * 192 * rec_out, waves=len(waves),
                          file_read_seconds=io_seconds["read"], file_write_seconds=io_seconds["write"], trace=trace)
     finally:
         _stop_pipeline(rt, wt, free_in, to_write)
@@ -840,7 +863,8 @@ def server_filter(ctx, in_path, out_path, width, height, weights, anchor=None, s
 # server_resize_plain: a separable resize with public weights over a pixel stream
 # ------------------------------------------------------------------------------------------------
 def server_resize_plain(ctx, in_path, out_path, width, height, dst_w, dst_h, kernel="catmull_rom", antialias=False, convention="half_pixel",
-                        weight_bits=None, rows_per_step=4, validate=True, rows=None, io_threads=8, int_coeffs=100, frac_coeffs=100, stats=None):
+                        weight_bits=None, rows_per_step=4, validate=True, rows=None, io_threads=8, int_coeffs=100, frac_coeffs=100, stats=None,
+                        out_primes=None):
     """Resize an encrypted image to dst_w x dst_h with PUBLIC interpolation weights (circuits.resample_axis_plan; Evaluator.remap): plaintext
     products and additions only, records stay at two polynomials.  The outputs are not the ciphertexts of server_resize (which encrypts the
     offsets and multiplies ciphertexts); with kernel="reference_cubic", convention="reference" they decrypt to the same image.
@@ -855,7 +879,11 @@ def server_resize_plain(ctx, in_path, out_path, width, height, dst_w, dst_h, ker
     again are moved to the front of the window.  The loop is synchronous, as server_filter's.
 
     rows=(y0, y1) produces a SHARD of the destination rows at its own position of the output stream, reading only the source rows it
-    needs: processes with disjoint row ranges fill one output file without any exchange."""
+    needs: processes with disjoint row ranges fill one output file without any exchange.
+
+    out_primes: None, or the number of primes the output records keep (1 .. k - 1): each step's result is mod-switched on the device before
+    its download and written with k = out_primes; the records belong to ctx.level(out_primes), where the client decrypts with
+    sk[:out_primes] (circuits.mod_switch_primes says how far a result with a given budget can go)."""
     import time
     from . import circuits
     from .evaluator import WeightTable
@@ -872,7 +900,9 @@ def server_resize_plain(ctx, in_path, out_path, width, height, dst_w, dst_h, ker
     tx, ty = tx.astype(np.int64), ty.astype(np.int64)
     ev = Evaluator(ctx)
     residues = _ResidueCheck(ctx, validate)
+    octx, out_primes = _out_level(ctx, out_primes)
     rec = RECORD_HEADER + 2 * ctx.k * ctx.n * 8
+    rec_out = RECORD_HEADER + 2 * octx.k * octx.n * 8
     own_in, own_out = not isinstance(in_path, StreamFile), not isinstance(out_path, StreamFile)
     if (in_path.size if not own_in else os.path.getsize(in_path)) < width * height * 3 * rec:
         raise EOFError("ciphertext stream ended")
@@ -902,14 +932,16 @@ def server_resize_plain(ctx, in_path, out_path, width, height, dst_w, dst_h, ker
     fresh = torch.empty((max_rows, width, 3) + shape, dtype=torch.int64, device=ctx.device)        # a step's new rows as uploaded
     hin = _pinned(("rsp_in",), (max_rows, width, 3) + shape)
     max_px = rows_per_step * dst_w
-    hout = _pinned(("rsp_out",), (max_px, 3) + shape)
+    oshape = (2, octx.k, octx.n)
+    hout = _pinned(("rsp_out",), (max_px, 3) + oshape)
     dout = torch.empty((max_px, 3) + shape, dtype=torch.int64, device=ctx.device)
+    dlow = torch.empty((max_px, 3) + oshape, dtype=torch.int64, device=ctx.device) if out_primes else dout       # what leaves for the host
     fin = StreamFile(in_path) if own_in else in_path
     fout = None
     t0, seconds = time.perf_counter(), {"read": 0.0, "write": 0.0}
     try:
-        fout = StreamFile(out_path, write=True, size=dst_w * dst_h * 3 * rec) if own_out else out_path
-        if fout.size < dst_w * dst_h * 3 * rec:
+        fout = StreamFile(out_path, write=True, size=dst_w * dst_h * 3 * rec_out) if own_out else out_path
+        if fout.size < dst_w * dst_h * 3 * rec_out:
             raise ValueError("output stream file is smaller than the result")
         lo = hi = spans[0][0]                                                                # resident source rows [lo, hi)
         for (y0, y1), (first, cnt) in zip(steps, spans):
@@ -938,16 +970,18 @@ def server_resize_plain(ctx, in_path, out_path, width, height, dst_w, dst_h, ker
             v_wids = np.ascontiguousarray(np.broadcast_to(idy[y0:y1, None, None, :], (y1 - y0, dst_w, 3, ty.shape[1]))).reshape(-1, ty.shape[1])
             npx = (y1 - y0) * dst_w
             ev.remap(table_y, resident[:hi - lo].view(-1, *shape), v_taps, v_wids, out=dout[:npx].view(-1, *shape), src_is_ntt=True)
-            hout[:npx].copy_(dout[:npx], non_blocking=True)
+            if out_primes:
+                ev.mod_switch(dout[:npx], out_primes, out=dlow[:npx])
+            hout[:npx].copy_(dlow[:npx], non_blocking=True)
             torch.cuda.current_stream().synchronize()                                        # hin may be refilled, hout has landed
             t_io = time.perf_counter()
-            fout.transfer(y0 * dst_w * 3, npx * 3, 2, ctx, hout, io_threads)
+            fout.transfer(y0 * dst_w * 3, npx * 3, 2, octx, hout, io_threads)
             seconds["write"] += time.perf_counter() - t_io
         residues.verdict(_refuser(own_out, fout, out_path))
         if stats is not None:
             stats.update(seconds=time.perf_counter() - t0, steps=len(steps), file_read_seconds=seconds["read"], file_write_seconds=seconds["write"],
                          resident_rows=max_rows, dst_w=dst_w, dst_h=dst_h, taps=(int(tx.shape[1]), int(ty.shape[1])),
-                         distinct_weights=(table_x.distinct, table_y.distinct))
+                         distinct_weights=(table_x.distinct, table_y.distinct), bytes_out=(row1 - row0) * dst_w * 3 * rec_out)
     finally:
         torch.cuda.synchronize()
         if own_in:

@@ -83,7 +83,8 @@ const char *fhe_last_error(void);
  *      and for fhe_weight_table_*, fhe_remap* and fhe_resample_axis_plan (resampling with public weights), and for fhe_batch_encode /
  *      fhe_batch_decode, fhe_galois_element and fhe_apply_galois (batched slots and Galois rotations), and for fhe_block8x8_plan_create /
  *      destroy, fhe_block8x8_scalar, fhe_channel_mix and fhe_dct8_matrix (integer linear maps across slot-packed ciphertexts), and for
- *      fhe_plane_map_plan_create / destroy / info and fhe_plane_map (sparse integer maps across position-packed ciphertexts).
+ *      fhe_plane_map_plan_create / destroy / info and fhe_plane_map (sparse integer maps across position-packed ciphertexts), and for
+ *      fhe_ctx_create_level and fhe_mod_switch (modulus switching: dropping RNS primes from ciphertexts).
  * A host compiled against this header compares fhe_abi_version() with FHE_ABI_VERSION before anything else (the Python
  * binding and seal/seal.h do). */
 #define FHE_ABI_VERSION 4
@@ -96,6 +97,10 @@ uint32_t fhe_abi_version(void);
  * built on the host and uploaded to `device`. */
 int fhe_ctx_create(uint32_t n, const uint64_t *q, uint32_t k, uint64_t t, int device, fhe_ctx **out);
 int fhe_ctx_destroy(fhe_ctx *ctx);
+/* The context a fhe_mod_switch result lives in: on the parent's device, with the parent's n and t, its first k_out primes (1 <= k_out < k) and
+ * the experiment switches the parent was created with (the environment is not read again).  A context of its own: the caller destroys it,
+ * before or after the parent.  A secret key [k][n] of the parent restricted to its first k_out rows is the same key there. */
+int fhe_ctx_create_level(const fhe_ctx *parent, uint32_t k_out, fhe_ctx **out);
 /* 1 once the lazily built ct x ct tables exist (diagnostic: a context that only ran linear circuits reports 0) */
 int fhe_ctx_has_ctct_tables(const fhe_ctx *ctx);
 /* the device the context was created on; fhe_ctx_bind_thread makes it the calling thread's current device (hipSetDevice) */
@@ -400,6 +405,23 @@ int fhe_plane_map_plan_destroy(fhe_plane_map_plan *plan);
 int fhe_plane_map_plan_info(const fhe_plane_map_plan *plan, uint32_t *groups, uint64_t *source_reads, uint32_t *window);
 int fhe_plane_map(const fhe_ctx *ctx, const fhe_plane_map_plan *plan, const uint64_t *in, uint64_t *out, uint32_t size, uint64_t count,
                   fhe_stream stream);
+
+/* ---- modulus switching: drop the last primes of the coefficient modulus -----------------------------------------------------------
+ * A result that has budget to spare does not need all k primes: switched to the first k_out it decrypts to the same plaintext under the
+ * same secret key (restricted to those primes) in a context made by fhe_ctx_create_level, with k_out / k of the bytes.  New entry points only.
+ *
+ * One drop removes the last prime p = q_m of a base q_0 .. q_m, per coefficient: with c the canonical representative in [0, q) and
+ * h = floor(p / 2),  c' = floor((c + h) / p) mod (q / p);  in residues, with r = (c_m + h) mod p, for i < m
+ *     c'_i = (c_i + (h mod q_i) - (r mod q_i)) * p^-1 mod q_i        (fully reduced)
+ * (SEAL 3.x divide_and_round_q_last).  fhe_mod_switch: in [n_polys][k][n] -> out [n_polys][k_out][n] is that drop applied k - k_out times,
+ * last prime first, to every coefficient of every polynomial: the iteration is the definition, not one rounding by the product of the
+ * dropped primes.  One kernel, no scratch, no allocation (csrc/modswitch.hip).
+ * Noise: a ciphertext of `size` polynomials under a ternary secret with invariant noise budget B has, after the switch, at least
+ *     -log2(2^-B + sum over the bases q' passed through of t S / q'),   S = 1 + n + .. + n^(size - 1)
+ * bits (circuits.mod_switch_budget in the Python host).
+ * Refused (FHE_ERR_PARAM) before anything is enqueued: k_out == 0 or k_out >= k, a null pointer, any overlap of the input and output ranges
+ * (the strides differ: there is no in-place form).  n_polys == 0 is a no-op. */
+int fhe_mod_switch(const fhe_ctx *ctx, uint32_t k_out, const uint64_t *in, uint64_t *out, uint64_t n_polys, fhe_stream stream);
 
 /* ---- fused block circuit: encrypted_dct (homo/fhe_image.h:196-288) followed by quantize_fhe
  * (homo/fhe_image.h:294-305) on n_blocks independent 8x8 blocks.  in/out: [n_blocks][64][2][k][n].
