@@ -145,6 +145,12 @@ struct fhe_dct_plan {
 // half-pixel shift in double before the store): shared by fhe_resize_sample_plan / fhe_resize_source_rows and fhe_resample_axis_plan
 inline float fhe_resize_ref_coord(u32 i, u32 dst_len, u32 src_len) { return (float)((float)i / (float)(dst_len - 1) * (float)src_len - 0.5); }
 
+// do [a, a + a_words) and [b, b + b_words) share a 64-bit word (operand checks of packed.hip, planemap.hip and tap_sum.h)
+static inline bool overlap(const void *a, u64 a_words, const void *b, u64 b_words) {
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + a_words * 8, b0 = (uintptr_t)b, b1 = b0 + b_words * 8;
+    return a0 < b1 && b0 < a1;
+}
+
 #define DISPATCH_L(logn, ...)                                                    \
     switch (logn) {                                                              \
         case 10: { constexpr int L = 10; __VA_ARGS__; } break;                   \

@@ -47,7 +47,3 @@ static inline PkMods pk_mods(const fhe_ctx *c) {
     for (u32 i = 0; i < c->k; i++) M.q[i] = c->qb.primes[i];
     return M;
 }
-static inline bool overlap(const void *a, u64 a_words, const void *b, u64 b_words) {
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + a_words * 8, b0 = (uintptr_t)b, b1 = b0 + b_words * 8;
-    return a0 < b1 && b0 < a1;
-}

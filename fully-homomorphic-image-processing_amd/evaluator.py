@@ -838,20 +838,38 @@ class Evaluator:
         _lib.call("fhe_ycc_to_rgb_blocks", self.ctx.h, _ptr(blocks), n_blocks, int_coeffs, frac_coeffs, _stream())
         return blocks
 
+    def _check_src(self, name, owner, what, src):
+        """filter2d / remap: `src` is [..., size, k, n] on this context and `owner` (the plan / weight table, `what` in the message)
+        belongs to it.  Returns (size, n_src)."""
+        kn = (self.ctx.k, self.ctx.n)
+        if not (isinstance(src, torch.Tensor) and src.dim() >= 4 and tuple(src.shape[-2:]) == kn and src.dtype == torch.int64 and src.is_contiguous()
+                and src.device == self.ctx.device and src.shape[-3] >= 1):
+            raise ValueError("%s: `src` must be a contiguous int64 tensor [..., size, k, n] = [..., size, %d, %d] on the context's device, got %r"
+                             % ((name,) + kn + (tuple(getattr(src, "shape", ())),)))
+        if owner.ctx is not self.ctx:
+            raise ValueError("%s: the %s was built for another context" % (name, what))
+        size = int(src.shape[-3])
+        return size, src.numel() // (size * kn[0] * kn[1])
+
+    def _check_out(self, name, src, out, count, size):
+        """filter2d / remap: `out` is [count, size, k, n] beside `src` and does not overlap it; allocated when None"""
+        shape = (count, size, self.ctx.k, self.ctx.n)
+        if out is None:
+            return torch.empty(shape, dtype=torch.int64, device=src.device)
+        if not (isinstance(out, torch.Tensor) and tuple(out.shape) == shape and out.dtype == torch.int64 and out.is_contiguous() and out.device == src.device):
+            raise ValueError("%s: `out` must be a contiguous int64 tensor %r on the device of `src`, got %r" % (name, shape, tuple(getattr(out, "shape", ()))))
+        a0, a1 = src.data_ptr(), src.data_ptr() + src.numel() * 8
+        b0, b1 = out.data_ptr(), out.data_ptr() + out.numel() * 8
+        if out.numel() and a0 < b1 and b0 < a1:
+            raise ValueError("%s: `out` overlaps `src`" % name)
+        return out
+
     def filter2d(self, plan, src, taps, out=None, src_is_ntt=False):
         """2-D convolution with public weights (fhe_filter2d, include/fhe_hip.h): output c = the sum over the kernel positions p of
         multiply_plain(src[taps[c][p]], encode(w[p])), bit for bit the op-by-op composition, with one forward transform per source
         and one inverse transform per output.  src: [n_src, size, k, n] (never written); taps: [count][kw * kh] indices into src
         (circuits.filter_tap_plan); returns [count, size, k, n].  src_is_ntt: src already is ntt_forward of the ciphertexts."""
-        kn = (self.ctx.k, self.ctx.n)
-        if not (isinstance(src, torch.Tensor) and src.dim() >= 4 and tuple(src.shape[-2:]) == kn and src.dtype == torch.int64 and src.is_contiguous()
-                and src.device == self.ctx.device and src.shape[-3] >= 1):
-            raise ValueError("filter2d: `src` must be a contiguous int64 tensor [..., size, k, n] = [..., size, %d, %d] on the context's device, got %r"
-                             % (kn + (tuple(getattr(src, "shape", ())),)))
-        if plan.ctx is not self.ctx:
-            raise ValueError("filter2d: the plan was built for another context")
-        size = int(src.shape[-3])
-        n_src = src.numel() // (size * kn[0] * kn[1])
+        size, n_src = self._check_src("filter2d", plan, "plan", src)
         width = plan.kw * plan.kh
         t = np.asarray(taps)
         if t.ndim != 2 or t.shape[1] != width or t.dtype.kind not in "iu":
@@ -860,16 +878,7 @@ class Evaluator:
             raise ValueError("filter2d: taps must index the %d source ciphertexts, got values in [%d, %d]" % (n_src, int(t.min()), int(t.max())))
         t = np.ascontiguousarray(t, dtype=np.uint32)
         count = int(t.shape[0])
-        shape = (count, size) + kn
-        if out is not None:
-            if not (isinstance(out, torch.Tensor) and tuple(out.shape) == shape and out.dtype == torch.int64 and out.is_contiguous() and out.device == src.device):
-                raise ValueError("filter2d: `out` must be a contiguous int64 tensor %r on the device of `src`, got %r" % (shape, tuple(getattr(out, "shape", ()))))
-            a0, a1 = src.data_ptr(), src.data_ptr() + src.numel() * 8
-            b0, b1 = out.data_ptr(), out.data_ptr() + out.numel() * 8
-            if out.numel() and a0 < b1 and b0 < a1:
-                raise ValueError("filter2d: `out` overlaps `src`")
-        else:
-            out = torch.empty(shape, dtype=torch.int64, device=src.device)
+        out = self._check_out("filter2d", src, out, count, size)
         if count == 0:
             return out
         nbytes = _lib.load().fhe_filter2d_scratch_bytes(self.ctx.h, plan.h, size, n_src, count, int(bool(src_is_ntt)))
@@ -884,15 +893,7 @@ class Evaluator:
         bit for bit the op-by-op composition.  src: [n_src, size, k, n] (never written); taps, wids: integer arrays [count][T]; returns
         [count, size, k, n].  src_is_ntt: src already is ntt_forward of the ciphertexts; out_is_ntt: the result is left as ntt_forward of
         the specified output (a second remap takes it with src_is_ntt)."""
-        kn = (self.ctx.k, self.ctx.n)
-        if not (isinstance(src, torch.Tensor) and src.dim() >= 4 and tuple(src.shape[-2:]) == kn and src.dtype == torch.int64 and src.is_contiguous()
-                and src.device == self.ctx.device and src.shape[-3] >= 1):
-            raise ValueError("remap: `src` must be a contiguous int64 tensor [..., size, k, n] = [..., size, %d, %d] on the context's device, got %r"
-                             % (kn + (tuple(getattr(src, "shape", ())),)))
-        if table.ctx is not self.ctx:
-            raise ValueError("remap: the weight table was built for another context")
-        size = int(src.shape[-3])
-        n_src = src.numel() // (size * kn[0] * kn[1])
+        size, n_src = self._check_src("remap", table, "weight table", src)
         t, w = np.asarray(taps), np.asarray(wids)
         if t.ndim != 2 or w.shape != t.shape or t.dtype.kind not in "iu" or w.dtype.kind not in "iu" or not 1 <= t.shape[1] <= REMAP_MAX_TAPS:
             raise ValueError("remap: `taps` and `wids` must be integer arrays of one shape [count][T], 1 <= T <= %d, got %r %s and %r %s"
@@ -907,16 +908,7 @@ class Evaluator:
         t = np.ascontiguousarray(np.where(live, t, 0), dtype=np.uint32)
         w = np.ascontiguousarray(w, dtype=np.uint32)
         count, width = int(t.shape[0]), int(t.shape[1])
-        shape = (count, size) + kn
-        if out is not None:
-            if not (isinstance(out, torch.Tensor) and tuple(out.shape) == shape and out.dtype == torch.int64 and out.is_contiguous() and out.device == src.device):
-                raise ValueError("remap: `out` must be a contiguous int64 tensor %r on the device of `src`, got %r" % (shape, tuple(getattr(out, "shape", ()))))
-            a0, a1 = src.data_ptr(), src.data_ptr() + src.numel() * 8
-            b0, b1 = out.data_ptr(), out.data_ptr() + out.numel() * 8
-            if out.numel() and a0 < b1 and b0 < a1:
-                raise ValueError("remap: `out` overlaps `src`")
-        else:
-            out = torch.empty(shape, dtype=torch.int64, device=src.device)
+        out = self._check_out("remap", src, out, count, size)
         if count == 0:
             return out
         nbytes = _lib.load().fhe_remap_scratch_bytes(self.ctx.h, table.h, size, n_src, count, int(bool(src_is_ntt)))

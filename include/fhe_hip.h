@@ -545,8 +545,8 @@ size_t fhe_filter2d_scratch_bytes(const fhe_ctx *ctx, const fhe_filter_plan *pla
 int fhe_filter2d(const fhe_ctx *ctx, const fhe_filter_plan *plan, const uint64_t *src, uint64_t n_src, uint32_t size, int src_is_ntt,
                  const uint32_t *taps, uint64_t *out, uint64_t count, void *scratch, size_t scratch_bytes, fhe_stream stream);
 /* which kernels fhe_filter2d launches after the forward transforms (labels in measurements; tests that must know what they ran):
- * 1 / 2 = k_filter_acc_inv_pm on the pseudo-Mersenne class 1 / 2 of the q-base (gather, lazy sums, products and the inverse transform
- * in one kernel), 0 = the general path k_filter_mac + fhe_ntt_inverse on Shoup arithmetic, 4 = the general path with the transforms
+ * 1 / 2 = k_tap_sum_pm on the pseudo-Mersenne class 1 / 2 of the q-base (gather, lazy sums, products and the inverse transform
+ * in one kernel), 0 = the general path k_tap_sum_mac + fhe_ntt_inverse on Shoup arithmetic, 4 = the general path with the transforms
  * on the exact-FP64 kernels (where fhe_ntt_forward runs them: n = 4096, primes <= 40 bits). */
 int fhe_filter_path(const fhe_ctx *ctx);
 
@@ -595,9 +595,9 @@ size_t fhe_remap_scratch_bytes(const fhe_ctx *ctx, const fhe_weight_table *table
 int fhe_remap(const fhe_ctx *ctx, const fhe_weight_table *table, const uint64_t *src, uint64_t n_src, uint32_t size, int src_is_ntt,
               const uint32_t *taps, const uint32_t *wids, uint32_t T, uint64_t *out, int out_is_ntt, uint64_t count, void *scratch,
               size_t scratch_bytes, fhe_stream stream);
-/* which kernels fhe_remap launches after the forward transforms: 1 / 2 = k_remap_acc_pm on the pseudo-Mersenne class 1 / 2 of the
+/* which kernels fhe_remap launches after the forward transforms: 1 / 2 = k_tap_sum_pm on the pseudo-Mersenne class 1 / 2 of the
  * q-base (gather, lazy sums, products and -- unless out_is_ntt -- the inverse transform in one kernel), 0 = the general path
- * k_remap_mac (+ fhe_ntt_inverse) on Shoup arithmetic, 4 = the general path with the transforms on the exact-FP64 kernels. */
+ * k_tap_sum_mac (+ fhe_ntt_inverse) on Shoup arithmetic, 4 = the general path with the transforms on the exact-FP64 kernels. */
 int fhe_remap_path(const fhe_ctx *ctx);
 
 /* Index and weight arithmetic of ONE axis of a separable resize (host only, no context, callable without a device).  Writes

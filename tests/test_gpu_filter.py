@@ -93,7 +93,7 @@ def test_filter_matches_oracle(fhe, oracle_mod, preset, switches, path, kernel, 
 
 
 def test_filter_on_pseudo_mersenne_class_2(fhe, oracle_mod):
-    """58-bit primes: k_filter_acc_inv_pm on class PmB (products below 1.5 q), including the all-(q - 1) sums"""
+    """58-bit primes: k_tap_sum_pm on class PmB (products below 1.5 q), including the all-(q - 1) sums"""
     import torch
     n = 2048
     ctx, orc = _pair(fhe, oracle_mod, (n, tuple(_primes_58(n, 2)), 1 << 14))
@@ -112,6 +112,42 @@ def test_filter_on_pseudo_mersenne_class_2(fhe, oracle_mod):
         coeff = fhe.to_host(ev.ntt_inverse(top))
         assert np.array_equal(out[7], ops.output(coeff, taps[7], weights)), kernel
     torch.cuda.synchronize()
+
+
+def test_plain_workgroup_order_gives_the_same_bits(fhe, oracle_mod):
+    """FHE_FILTER_XCD=0 (the shared-ids rows in plain workgroup order, the launch arm only this switch reaches) against the default
+    order, at a grid that is no multiple of the eight XCDs: idle workgroups and outputs that straddle XCD runs"""
+    import torch
+    ctx, orc = _pair(fhe, oracle_mod, "SEAL23_4096")
+    plain, _ = _pair(fhe, oracle_mod, "SEAL23_4096", FHE_FILTER_XCD="0")
+    assert _path(fhe, ctx) == 1 and _path(fhe, plain) == 1
+    weights, anchor, stride = fo.KERNELS["gauss3"]
+    size = 3
+    taps = fo.tap_plan(3, 3, 1, 3, 3, anchor, stride)
+    assert len(taps) * size * ctx.k == 54 and 54 % 8 != 0
+    src = ctx.random_ct(9, size=size, seed=fhe.SEED + 54)
+    out = fhe.Evaluator(ctx).filter2d(fhe.FilterPlan(ctx, weights), src, taps)
+    assert torch.equal(out, fhe.Evaluator(plain).filter2d(fhe.FilterPlan(plain, weights), src, taps))
+    assert np.array_equal(fhe.to_host(out)[4], fo.OracleOps(orc).output(fhe.to_host(src), taps[4], weights))
+
+
+@pytest.mark.parametrize("kernel", ["sobel_x", "gauss5", "chroma420"])
+@pytest.mark.parametrize("preset,path", [("SMALL", 0), ("SEAL23_4096", 1), ("PM58", 2)])
+def test_filter2d_equals_remap(fhe, oracle_mod, preset, path, kernel):
+    """the identity the shared kernels rest on: fhe_filter2d is fhe_remap with every output naming the kernel positions 0 .. kw * kh - 1
+    as its weight ids (zero weights: skipped slots; equal weights: runs in the filter, single taps in the remap); both are exact"""
+    import torch
+    name = (2048, tuple(_primes_58(2048, 2)), 1 << 14) if preset == "PM58" else preset
+    ctx, _ = _pair(fhe, oracle_mod, name)
+    assert _path(fhe, ctx) == path and fhe._lib.load().fhe_remap_path(ctx.h) == path
+    ev = fhe.Evaluator(ctx)
+    weights, anchor, stride = fo.KERNELS[kernel]
+    kh, kw = weights.shape
+    taps = fo.tap_plan(W, H, 1, kw, kh, anchor, stride)
+    src = ctx.random_ct(W * H, size=2, seed=fhe.SEED + 7)
+    wids = np.broadcast_to(np.arange(kw * kh, dtype=np.uint32), (len(taps), kw * kh))
+    filtered = ev.filter2d(fhe.FilterPlan(ctx, weights), src, taps)
+    assert torch.equal(filtered, ev.remap(fhe.WeightTable(ctx, weights.ravel()), src, taps, wids))
 
 
 @pytest.mark.parametrize("kernel", ["box7", "minus8x8"])
