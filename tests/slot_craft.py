@@ -3,8 +3,9 @@ with it that put chosen residues under the kernels' products and reductions.
 
 Everything here is integer arithmetic modulo each prime; no floating point is involved.  Residues are numpy uint64
 arrays shaped [..., k, n] (n slots in the CPU oracle's NTT order), centred values and sums of centred values are int64.
-A modular product of two residues below 2^48 is formed from limbs of 63 - bits(p) bits so that no intermediate leaves 64
-bits (test_slot_craft_cpu.py checks it against Python integers).
+A modular product of two residues is formed from limbs of 63 - bits(p) bits so that no intermediate leaves 64 bits, for
+primes of up to 57 bits (test_slot_craft_cpu.py checks it against Python integers up to 48 bits, test_dct_u64_craft_cpu.py
+up to 57).
 
 The model is slotwise, so the order in which the kernels hold the slots does not matter: a constant's slot value meets
 the data's value of the same slot in every order.
@@ -142,7 +143,7 @@ class SlotModel:
         self.Pi = self.P.astype(np.int64)
         self.H = (self.P - U(1)) // U(2)                            # (p - 1) / 2: the largest centred residue
         bits = max(p.bit_length() for p in self.q)
-        assert bits <= 48
+        assert bits <= 57                                           # limbs of at least 6 bits (dct_u64_craft.py: the fused u64 pair's primes)
         self.w = 63 - bits
         self.limbs = -(-bits // self.w)
         self.inv2 = (self.P + U(1)) // U(2)

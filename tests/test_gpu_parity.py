@@ -374,7 +374,9 @@ def test_dct_fp64_fused_at_n2048(fhe, oracle_mod, monkeypatch):
 
 @pytest.mark.parametrize("preset", ["SEAL23_4096", "P8192"])
 def test_dct_extreme_residues_u64_fused(fhe, oracle_mod, preset):
-    """all-(q-1) inputs through the lazy ranges of the fused u64 kernels (values up to 128 q before the scale product)"""
+    """all-(q-1) inputs through the lazy ranges of the fused u64 kernels (values up to 128 q before the scale product).  All-(q-1) inputs
+    are the largest inputs, not the worst case of those ranges, and meet none of the values the exits are delicate for: prescribed outputs,
+    exact zeros, the widest operands and every instantiation are in tests/test_gpu_dct_u64_extremes.py."""
     ctx, orc = _pair(fhe, oracle_mod, preset)
     ev = fhe.Evaluator(ctx)
     blk = np.zeros((1, 64, 2, ctx.k, ctx.n), dtype=np.uint64)
@@ -834,7 +836,8 @@ def test_u64_lazy_ranges_at_boundary_prime_sizes(fhe, oracle_mod, bits, n):
     doubled Harvey ranges [0, 8q) above; the fused u64 DCT is lazy up to 56 bits and keeps one subtraction per
     butterfly at 57.  The LARGEST prime of each size with all-(q-1) inputs: the largest INPUTS the kernels take -- not the worst
     case of the lazy ranges (random data comes closer to the static bounds in almost every stage); the transforms at
-    their arithmetic edges are in tests/test_gpu_ntt_extremes.py."""
+    their arithmetic edges are in tests/test_gpu_ntt_extremes.py, the fused u64 DCT pair at 55, 56 and 57 bits and at all three n in
+    tests/test_gpu_dct_u64_extremes.py."""
     q = [_largest_ntt_prime_below(bits, n), _largest_ntt_prime_below(bits - 1, n)]
     ctx, orc = fhe.SEALContext(n, q, 1 << 14), oracle_mod.Oracle(n, q, 1 << 14)
     ev = fhe.Evaluator(ctx)
