@@ -17,8 +17,14 @@
 //                       40 bytes per thread and polynomial for primes <= 37 bits, FP64 otherwise)
 //   kernel B (columns): same for columns on the NTT-form intermediates, per-output scale
 //                       encode(0.125)*encode(1/quant) folded into one product, inverse NTT, store.
-// The public u64 ciphertexts are read and written 8 bytes per lane (a thread owns coefficients r*TP + tid, never two
-// neighbours).  The private formats are laid out so that the column kernel moves 16 bytes per lane (`buffer_load_dwordx4`,
+// The public u64 ciphertexts are read and written 16 bytes per lane as well, in the shapes with 8 coefficients per thread
+// (n = 2048, 4096, 8192): in the ordinary pass-0 layout a thread owns coefficients r*TP + tid, never two neighbours, but
+// pass 0 is column-independent, so the wide kernels (WIDE) carry two neighbouring columns of two polynomials through it
+// instead of one column of four -- coefficients r*TP + 2u + {0, 1} of polynomials 2h + {0, 1}, h = tid / (TP/2) -- and
+// the exchange between pass 0 and pass 1 converts between the two layouts (exchange_pairs_fwd / _inv).  The arithmetic
+// per value is unchanged.  The 8-byte bodies remain: 16 coefficients per thread, n = 1024, k_dct_one_launch, a call
+// whose `in` or `out` is only 8-byte aligned (fhe_dct_f64_launch) and FHE_DCT_WIDE_IO=0.
+// The private formats are laid out so that the column kernel moves 16 bytes per lane (`buffer_load_dwordx4`,
 // 1 KiB contiguous per wave): the packed intermediate as two 16-byte planes of low words and one 8-byte plane of high
 // bytes (store_packed), the FP64 intermediate as planes of value pairs, the packed column kernel's constants as tables of
 // pairs (k_consts_to_pairs).  Slot ownership, the transforms and every arithmetic operation are those of the 8-byte layout.
@@ -50,6 +56,9 @@ template <int LO, int LE> __device__ __forceinline__ int g_index(int tid, int r)
     return ((tid >> LO) << (LO + LE)) | (r << LO) | (tid & ((1 << LO) - 1));
 }
 template <int LO, int LE> __device__ __forceinline__ int g_pad(int j) { return j + ((j >> (LO + LE)) << LO); }
+// paired pass-0 layout (exchange_pairs_fwd): h = tid / (TP/2).  The halves of a workgroup are whole waves, so h is the same
+// for every lane of a wave and lives in a scalar register: what depends on it costs scalar instructions only.
+template <int TP> __device__ __forceinline__ int pair_half(int tid) { return __builtin_amdgcn_readfirstlane(tid) / (TP / 2); }
 
 // twiddles of one register pass, fetched ahead of use (before the preceding LDS barrier) so that
 // their L2 latency is hidden behind the previous pass: 2^(LE-1-rb) values per stage, < 2^LE in all.
@@ -180,9 +189,82 @@ __device__ __forceinline__ void transpose(double (&x)[M][1 << LE], double *lds, 
     }
 }
 
+// The paired pass-0 layout (PAIRED transforms: the wide row and column kernels).  Pass 0 is column-independent and its
+// twiddles are the same for every thread, so the 4 x 2^LE values a thread carries through it need not be one column of
+// four polynomials: with h = tid / (TP/2), u = tid % (TP/2) a thread holds, for j = 0, 1 and c = 0, 1,
+//     x[2j + c][r] = coefficient r*TP + 2u + c of polynomial 2h + j
+// -- two neighbouring columns of two polynomials, which it reads from / writes to a public ciphertext 16 bytes at a time.
+// The exchange next to pass 0, the one that crosses waves and needs workgroup barriers anyway, converts between this
+// and the ordinary pass-1 layout (x[m][r] = coefficient g_index<LO1>(tid, r) of polynomial m) through BOTH buffers at
+// once: in step j polynomial j travels through buffer 0 and polynomial 2 + j through buffer 1, so on the paired side
+// threads with h = 0 touch buffer 0 and threads with h = 1 buffer 1, 16 bytes per access (the pair is adjacent and 16-byte
+// aligned under g_pad<LO1>: the padding is 2^LO1 words every TP).  Three barriers where four transposes have four.
+// Hazards.  Step 1 reuses both buffers: one barrier between the steps.  Towards the neighbouring exchange (pass 1 <-> 2)
+// there is none when that exchange is wave-local: on the ordinary side a wave touches only words of the region
+// [576 w, 576 (w + 1)) that the same wave -- and no other -- uses in the wave-local exchanges, under either padding
+// (tests/test_dct_paired_layout.py), and LDS operations of one wave complete in order.  Where the neighbour crosses waves
+// itself (n = 8192: LO1 = 7) its last / first access to a buffer is separated from ours by one more barrier.
+template <int L, int LE>
+__device__ __forceinline__ void exchange_pairs_fwd(double (&x)[4][1 << LE], double *lds, int tid) {
+    using SH = Shape<L, LE>;
+    constexpr int TP = SH::TP, E = 1 << LE, LO1 = g_lo(L, LE, 1), LO2 = g_lo(L, LE, 2);
+    constexpr bool NEIGHBOUR_WAVE_LOCAL = (TP <= 64) || (LO1 <= 6 && LO2 <= 6);
+    static_assert(LE == 3 && TP >= 128 && g_lo(L, LE, 0) == LO1 + LE, "paired layout: 8 values per thread, halves of whole waves");
+    const int h = pair_half<TP>(tid), u = tid % (TP / 2);
+    double *wr = lds + h * SH::LDS_WORDS + 2 * u;                      // + r * (TP + 2^LO1) = g_pad<LO1>(r*TP + 2u)
+    const double *rd = lds + g_pad<LO1, LE>(g_index<LO1, LE>(tid, 0));  // + r * 2^LO1
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        if (j) __syncthreads();                 // every wave has read step 0
+#pragma unroll
+        for (int r = 0; r < E; r++) *(double2 *)(wr + r * (TP + (1 << LO1))) = make_double2(x[2 * j][r], x[2 * j + 1][r]);
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < E; r++) {
+            x[2 * j][r] = rd[r << LO1];                                // polynomial j
+            x[2 * j + 1][r] = rd[SH::LDS_WORDS + (r << LO1)];          // polynomial 2 + j
+        }
+    }
+    if constexpr (!NEIGHBOUR_WAVE_LOCAL) __syncthreads();
+    // x[0], x[1], x[2], x[3] hold polynomials 0, 2, 1, 3: put them in order (register renaming, the loops are unrolled)
+#pragma unroll
+    for (int r = 0; r < E; r++) { const double t = x[1][r]; x[1][r] = x[2][r]; x[2][r] = t; }
+}
+// the mirror image: ordinary pass-1 layout in, paired layout out
+template <int L, int LE>
+__device__ __forceinline__ void exchange_pairs_inv(double (&x)[4][1 << LE], double *lds, int tid) {
+    using SH = Shape<L, LE>;
+    constexpr int TP = SH::TP, E = 1 << LE, LO1 = g_lo(L, LE, 1), LO2 = g_lo(L, LE, 2);
+    constexpr bool NEIGHBOUR_WAVE_LOCAL = (TP <= 64) || (LO1 <= 6 && LO2 <= 6);
+    static_assert(LE == 3 && TP >= 128 && g_lo(L, LE, 0) == LO1 + LE, "paired layout: 8 values per thread, halves of whole waves");
+    const int h = pair_half<TP>(tid), u = tid % (TP / 2);
+    double *wr = lds + g_pad<LO1, LE>(g_index<LO1, LE>(tid, 0));
+    const double *rd = lds + h * SH::LDS_WORDS + 2 * u;
+    if constexpr (!NEIGHBOUR_WAVE_LOCAL) __syncthreads();
+#pragma unroll
+    for (int r = 0; r < E; r++) { const double t = x[1][r]; x[1][r] = x[2][r]; x[2][r] = t; }      // polynomials 0, 2, 1, 3
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        if (j) __syncthreads();
+#pragma unroll
+        for (int r = 0; r < E; r++) {
+            wr[r << LO1] = x[2 * j][r];                                // polynomial j
+            wr[SH::LDS_WORDS + (r << LO1)] = x[2 * j + 1][r];          // polynomial 2 + j
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < E; r++) {
+            const double2 v = *(const double2 *)(rd + r * (TP + (1 << LO1)));
+            x[2 * j][r] = v.x;
+            x[2 * j + 1][r] = v.y;
+        }
+    }
+}
+
 // forward transform; `w` holds the pass-0 twiddles on entry.  `pre()` is invoked once, right
 // before the last transpose, so that the caller can start fetching what it needs after the NTT.
-template <int L, int LE, int M, typename PRE, int P = 0>
+// PAIRED: x enters in the paired pass-0 layout (exchange_pairs_fwd) and leaves in the ordinary last-pass layout.
+template <int L, int LE, int M, bool PAIRED = false, typename PRE, int P = 0>
 __device__ __forceinline__ void ntt_fwd(double (&x)[M][1 << LE], double (&w)[(1 << LE) - 1], const double *__restrict__ tw, double p, double pinv,
                                         double *lds, int tid, int &phase, PRE pre) {
     if constexpr (P + 1 < Shape<L, LE>::NP) {
@@ -191,13 +273,15 @@ __device__ __forceinline__ void ntt_fwd(double (&x)[M][1 << LE], double (&w)[(1 
         fwd_pass<L, LE, P, M>(x, w, p, pinv);
         if (LE < 4) load_tw<L, LE, P + 1>(wn, tw, tid);    // four waves/SIMD: the transpose alone hides it
         if constexpr (P + 2 == Shape<L, LE>::NP) pre();
-        transpose<L, LE, g_lo(L, LE, P), g_lo(L, LE, P + 1), M>(x, lds, tid, phase);
-        ntt_fwd<L, LE, M, PRE, P + 1>(x, wn, tw, p, pinv, lds, tid, phase, pre);
+        if constexpr (PAIRED && P == 0) exchange_pairs_fwd<L, LE>(x, lds, tid);
+        else transpose<L, LE, g_lo(L, LE, P), g_lo(L, LE, P + 1), M>(x, lds, tid, phase);
+        ntt_fwd<L, LE, M, PAIRED, PRE, P + 1>(x, wn, tw, p, pinv, lds, tid, phase, pre);
     } else {
         fwd_pass<L, LE, P, M>(x, w, p, pinv);
     }
 }
-template <int L, int LE, int M, bool BIG, int P = Shape<L, LE>::NP - 1>
+// PAIRED: x enters in the ordinary last-pass layout and leaves in the paired pass-0 layout (exchange_pairs_inv).
+template <int L, int LE, int M, bool BIG, bool PAIRED = false, int P = Shape<L, LE>::NP - 1>
 __device__ __forceinline__ void ntt_inv(double (&x)[M][1 << LE], double (&w)[(1 << LE) - 1], const double *__restrict__ itw, double p, double pinv,
                                         double *lds, int tid, int &phase) {
     if constexpr (P > 0) {
@@ -211,8 +295,9 @@ __device__ __forceinline__ void ntt_inv(double (&x)[M][1 << LE], double (&w)[(1 
 #pragma unroll
                 for (int r = 0; r < (1 << LE); r++) x[m][r] = red(x[m][r], p, pinv);
         }
-        transpose<L, LE, g_lo(L, LE, P), g_lo(L, LE, P - 1), M>(x, lds, tid, phase);
-        ntt_inv<L, LE, M, BIG, P - 1>(x, wn, itw, p, pinv, lds, tid, phase);
+        if constexpr (PAIRED && P == 1) exchange_pairs_inv<L, LE>(x, lds, tid);
+        else transpose<L, LE, g_lo(L, LE, P), g_lo(L, LE, P - 1), M>(x, lds, tid, phase);
+        ntt_inv<L, LE, M, BIG, PAIRED, P - 1>(x, wn, itw, p, pinv, lds, tid, phase);
     } else {
         inv_pass<L, LE, P, M>(x, w, itw[0], p, pinv);
     }
@@ -279,7 +364,8 @@ __device__ __forceinline__ void stage_consts(gwin_t w, u32 voff, u32 soff, u32 c
     }
 }
 
-template <int L, int LE, bool BIG, int HALF, bool PACK, bool LDSC>
+// WIDE: the public inputs 16 bytes per lane, in the paired pass-0 layout (exchange_pairs_fwd); `in` must be 16-byte aligned
+template <int L, int LE, bool BIG, int HALF, bool PACK, bool LDSC, bool WIDE = false>
 __device__ __forceinline__ void rows_body(const u64 *__restrict__ in, double *__restrict__ mid, const double *__restrict__ consts,
                                           const double *__restrict__ tw, const Work &wk, double p, double pinv, u32 k, double *lds) {
     using SH = Shape<L, LE>;
@@ -312,7 +398,34 @@ __device__ __forceinline__ void rows_body(const u64 *__restrict__ in, double *__
             x[m][r] = HALF ? u52_biased(A) - u52_biased(B) : u52_to_f64(A + B);
         }
     };
-    if constexpr (LE >= 4) {
+    if constexpr (WIDE) {
+        // paired pass-0 mapping: polynomial 2h + j (= d_(2h+j) +- d_(7-2h-j)), coefficients r*TP + 2u + {0, 1}.  The two
+        // ciphertext offsets that depend on h are wave-uniform (pair_half); a wave reads 1 KiB contiguously per instruction.
+        // Staging stays at 32 VGPRs: four rows of a polynomial pair at a time.
+        const u32 h = (u32)pair_half<TP>(tid), vw = 16u * ((u32)tid % (TP / 2));
+        const u32 soa = h ? 2u * ctb : 0u, sob = h ? 4u * ctb : 6u * ctb;
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+#pragma unroll
+            for (int g = 0; g < E / 4; g++) {
+                u64x2 qa[4], qb[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    qa[i] = gld_u64x2(win_in, vw, soa + (u32)j * ctb + (4 * g + i) * TP * 8);
+                    qb[i] = gld_u64x2(win_in, vw, sob + (u32)(1 - j) * ctb + (4 * g + i) * TP * 8);
+                }
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    x[2 * j][4 * g + i] = HALF ? u52_biased(qa[i].a) - u52_biased(qb[i].a) : u52_to_f64(qa[i].a + qb[i].a);
+                    x[2 * j + 1][4 * g + i] = HALF ? u52_biased(qa[i].b) - u52_biased(qb[i].b) : u52_to_f64(qa[i].b + qb[i].b);
+                }
+                // the group's values are consumed here, so they are formed (and its 32 staging registers free) before the
+                // next group is requested: a bare fence keeps the loads in order but lets hipcc sink every combine below them
+                asm volatile("" ::"v"(x[2 * j][4 * g]), "v"(x[2 * j][4 * g + 1]), "v"(x[2 * j][4 * g + 2]), "v"(x[2 * j][4 * g + 3]),
+                             "v"(x[2 * j + 1][4 * g]), "v"(x[2 * j + 1][4 * g + 1]), "v"(x[2 * j + 1][4 * g + 2]), "v"(x[2 * j + 1][4 * g + 3]) : "memory");
+            }
+        }
+    } else if constexpr (LE >= 4) {
         issue(0);
         issue(1);
         asm volatile("" ::: "memory");
@@ -341,7 +454,7 @@ __device__ __forceinline__ void rows_body(const u64 *__restrict__ in, double *__
         for (int i = 0; i < NC; i++) cn[i] = gld_f64(win_c, vo, (u32)i * csb + r * TP * 8);
     };
     int phase = 0;
-    ntt_fwd<L, LE, 4>(x, w0, tw, p, pinv, lds, tid, phase, [&] { if (LE >= 4) fetch(0); });
+    ntt_fwd<L, LE, 4, WIDE>(x, w0, tw, p, pinv, lds, tid, phase, [&] { if (LE >= 4) fetch(0); });
     // LDSC: two staging buffers of NC x 64 doubles per wave (9 x 512 B x 2 x 8 waves = the two exchange buffers exactly)
     const int lane = tid & 63;
     double *stg = lds + (tid >> 6) * (2 * NC * 64);
@@ -407,19 +520,20 @@ __host__ __device__ constexpr int occ_waves(int tp, int lds_words) {
 }
 template <int L, int LE> struct Occ { static constexpr int W = occ_waves(Shape<L, LE>::TP, Shape<L, LE>::LDS_WORDS); };
 
-template <int L, int LE, bool BIG, bool PACK, bool LDSC>
+template <int L, int LE, bool BIG, bool PACK, bool LDSC, bool WIDE = false>
 __global__ __launch_bounds__((Shape<L, LE>::TP), (Occ<L, LE>::W)) void k_dct_rows(const u64 *__restrict__ in, double *__restrict__ mid,
                                                                   const double *__restrict__ consts, const double *__restrict__ tw_all,
                                                                   const Modulus *__restrict__ mods, u32 k) {
-    __shared__ double lds[2 * Shape<L, LE>::LDS_WORDS];
+    __shared__ __attribute__((aligned(16))) double lds[2 * Shape<L, LE>::LDS_WORDS];
     const Work wk = decode(blockIdx.x, k);
     const double p = (double)mods[wk.prime].q, pinv = 1.0 / p;
     const double *tw = tw_all + (size_t)wk.prime * Shape<L, LE>::N;
-    if (wk.half) rows_body<L, LE, BIG, 1, PACK, LDSC>(in, mid, consts, tw, wk, p, pinv, k, lds);
-    else rows_body<L, LE, BIG, 0, PACK, LDSC>(in, mid, consts, tw, wk, p, pinv, k, lds);
+    if (wk.half) rows_body<L, LE, BIG, 1, PACK, LDSC, WIDE>(in, mid, consts, tw, wk, p, pinv, k, lds);
+    else rows_body<L, LE, BIG, 0, PACK, LDSC, WIDE>(in, mid, consts, tw, wk, p, pinv, k, lds);
 }
 
-template <int L, int LE, bool BIG, int HALF, bool PACK>
+// WIDE: the public outputs 16 bytes per lane, in the paired pass-0 layout (exchange_pairs_inv); `out` must be 16-byte aligned
+template <int L, int LE, bool BIG, int HALF, bool PACK, bool WIDE = false>
 __device__ __forceinline__ void cols_body(const double *__restrict__ mid, u64 *__restrict__ out, const double *__restrict__ consts,
                                           const double *__restrict__ cpairs, const double *__restrict__ itw, const Work &wk, double p, double pinv, u32 k, double *lds) {
     using SH = Shape<L, LE>;
@@ -528,24 +642,36 @@ __device__ __forceinline__ void cols_body(const double *__restrict__ mid, u64 *_
     // constants (requested before the slots, the kernel spills 4 VGPRs); four waves per SIMD hide the round trip
     if constexpr (PACK) load_tw<L, LE, LASTP>(wl, itw, tid);
     int phase = 0;
-    ntt_inv<L, LE, 4, BIG>(x, wl, itw, p, pinv, lds, tid, phase);
+    ntt_inv<L, LE, 4, BIG, WIDE>(x, wl, itw, p, pinv, lds, tid, phase);
+    if constexpr (WIDE) {
+        // paired pass-0 mapping: x[2j + c][r] = coefficient r*TP + 2u + c of output row 2 (2h + j) + HALF; the row offset
+        // that depends on h is wave-uniform (pair_half)
+        const u32 vw = 16u * ((u32)tid % (TP / 2)), sow = pair_half<TP>(tid) ? 4u * rsb : 0u;
 #pragma unroll
-    for (int m = 0; m < 4; m++) {
+        for (int j = 0; j < 2; j++) {
 #pragma unroll
-        for (int r = 0; r < E; r++) gst_u64(win_out, vo, (u32)(2 * m + HALF) * rsb + r * TP * 8, f64_to_residue(x[m][r], pbias));
+            for (int r = 0; r < E; r++)
+                gst_u64x2(win_out, vw, sow + (u32)(2 * j + HALF) * rsb + r * TP * 8, f64_to_residue(x[2 * j][r], pbias), f64_to_residue(x[2 * j + 1][r], pbias));
+        }
+    } else {
+#pragma unroll
+        for (int m = 0; m < 4; m++) {
+#pragma unroll
+            for (int r = 0; r < E; r++) gst_u64(win_out, vo, (u32)(2 * m + HALF) * rsb + r * TP * 8, f64_to_residue(x[m][r], pbias));
+        }
     }
 }
 
-template <int L, int LE, bool BIG, bool PACK>
+template <int L, int LE, bool BIG, bool PACK, bool WIDE = false>
 __global__ __launch_bounds__((Shape<L, LE>::TP), (Occ<L, LE>::W)) void k_dct_cols(const double *__restrict__ mid, u64 *__restrict__ out,
                                                                   const double *__restrict__ consts, const double *__restrict__ cpairs, const double *__restrict__ itw_all,
                                                                   const Modulus *__restrict__ mods, u32 k) {
-    __shared__ double lds[2 * Shape<L, LE>::LDS_WORDS];
+    __shared__ __attribute__((aligned(16))) double lds[2 * Shape<L, LE>::LDS_WORDS];
     const Work wk = decode(blockIdx.x, k);   // line = column index
     const double p = (double)mods[wk.prime].q, pinv = 1.0 / p;
     const double *itw = itw_all + (size_t)wk.prime * Shape<L, LE>::N;
-    if (wk.half) cols_body<L, LE, BIG, 1, PACK>(mid, out, consts, cpairs, itw, wk, p, pinv, k, lds);
-    else cols_body<L, LE, BIG, 0, PACK>(mid, out, consts, cpairs, itw, wk, p, pinv, k, lds);
+    if (wk.half) cols_body<L, LE, BIG, 1, PACK, WIDE>(mid, out, consts, cpairs, itw, wk, p, pinv, k, lds);
+    else cols_body<L, LE, BIG, 0, PACK, WIDE>(mid, out, consts, cpairs, itw, wk, p, pinv, k, lds);
 }
 
 // EXPERIMENT (round 4, FHE_DCT_ONE_LAUNCH=D; off by default): rows and columns in ONE launch.  A unit is (prime, block,
@@ -827,35 +953,52 @@ int fhe_dct_f64_make_consts(const fhe_ctx *c, fhe_dct_plan *plan, hipStream_t st
 // (The column kernel has four more constants per slot and no register to spare: the same staging spills 36-56 VGPRs
 // there and measured 68 k blocks/s against 80 k, so it keeps its loads.)
 
-template <int L, int LE>
-static void launch_pair(const fhe_ctx *c, const fhe_dct_plan *plan, const u64 *in, u64 *out, double *mid, unsigned grid, bool big, hipStream_t st, int which) {
+// The wide kernels (16-byte public accesses, paired pass-0 layout) exist for 8 coefficients per thread and workgroups of at
+// least two waves (n = 2048, 4096, 8192); everything else, and a call that does not ask for them, runs the 8-byte bodies.
+template <int L, int LE, bool BIG, bool PACK, bool LDSC>
+static void launch_rows(bool wide, const fhe_ctx *c, const fhe_dct_plan *plan, const u64 *in, double *mid, unsigned grid, hipStream_t st) {
     constexpr int TP = Shape<L, LE>::TP;
-    if constexpr (LE == 4) {
-        if (big) {
-            if (which & 1) k_dct_rows<L, LE, true, false, false><<<grid, TP, 0, st>>>(in, mid, plan->d_consts_f64, c->qb.d_tw_f64, c->qb.d_mod, c->k);
-            if (which & 2) k_dct_cols<L, LE, true, false><<<grid, TP, 0, st>>>(mid, out, plan->d_consts_f64, plan->d_consts_pair, c->qb.d_itw_f64, c->qb.d_mod, c->k);
+    if constexpr (LE == 3 && TP >= 128 && !(L == 12 && BIG)) {      // n = 4096 takes 16 coefficients per thread above 40 bits
+        if (wide) {
+            k_dct_rows<L, LE, BIG, PACK, LDSC, true><<<grid, TP, 0, st>>>(in, mid, plan->d_consts_f64, c->qb.d_tw_f64, c->qb.d_mod, c->k);
             return;
         }
+    }
+    k_dct_rows<L, LE, BIG, PACK, LDSC><<<grid, TP, 0, st>>>(in, mid, plan->d_consts_f64, c->qb.d_tw_f64, c->qb.d_mod, c->k);
+}
+template <int L, int LE, bool BIG, bool PACK>
+static void launch_cols(bool wide, const fhe_ctx *c, const fhe_dct_plan *plan, const double *mid, u64 *out, unsigned grid, hipStream_t st) {
+    constexpr int TP = Shape<L, LE>::TP;
+    if constexpr (LE == 3 && TP >= 128 && !(L == 12 && BIG)) {      // n = 4096 takes 16 coefficients per thread above 40 bits
+        if (wide) {
+            k_dct_cols<L, LE, BIG, PACK, true><<<grid, TP, 0, st>>>(mid, out, plan->d_consts_f64, plan->d_consts_pair, c->qb.d_itw_f64, c->qb.d_mod, c->k);
+            return;
+        }
+    }
+    k_dct_cols<L, LE, BIG, PACK><<<grid, TP, 0, st>>>(mid, out, plan->d_consts_f64, plan->d_consts_pair, c->qb.d_itw_f64, c->qb.d_mod, c->k);
+}
+
+// wide_in / wide_out: run the wide row / column kernel where the shape has one
+template <int L, int LE>
+static void launch_pair(const fhe_ctx *c, const fhe_dct_plan *plan, const u64 *in, u64 *out, double *mid, unsigned grid, bool big, hipStream_t st, int which,
+                        bool wide_in, bool wide_out) {
+    if (big) {
+        if (which & 1) launch_rows<L, LE, true, false, false>(wide_in, c, plan, in, mid, grid, st);
+        if (which & 2) launch_cols<L, LE, true, false>(wide_out, c, plan, mid, out, grid, st);
+        return;
     }
     if constexpr (LE == 3) {
-        if (big) {
-            if (which & 1) k_dct_rows<L, LE, true, false, false><<<grid, TP, 0, st>>>(in, mid, plan->d_consts_f64, c->qb.d_tw_f64, c->qb.d_mod, c->k);
-            if (which & 2) k_dct_cols<L, LE, true, false><<<grid, TP, 0, st>>>(mid, out, plan->d_consts_f64, plan->d_consts_pair, c->qb.d_itw_f64, c->qb.d_mod, c->k);
-            return;
-        }
         if (c->max_prime_bits <= 37 && c->opt.dct_pack) {      // packed intermediate, 40 instead of 64 bytes
             if (which & 1) {
-                if (c->opt.dct_ldsc) k_dct_rows<L, LE, false, true, true><<<grid, TP, 0, st>>>(in, mid, plan->d_consts_f64, c->qb.d_tw_f64, c->qb.d_mod, c->k);
-                else k_dct_rows<L, LE, false, true, false><<<grid, TP, 0, st>>>(in, mid, plan->d_consts_f64, c->qb.d_tw_f64, c->qb.d_mod, c->k);
+                if (c->opt.dct_ldsc) launch_rows<L, LE, false, true, true>(wide_in, c, plan, in, mid, grid, st);
+                else launch_rows<L, LE, false, true, false>(wide_in, c, plan, in, mid, grid, st);
             }
-            if (which & 2) k_dct_cols<L, LE, false, true><<<grid, TP, 0, st>>>(mid, out, plan->d_consts_f64, plan->d_consts_pair, c->qb.d_itw_f64, c->qb.d_mod, c->k);
+            if (which & 2) launch_cols<L, LE, false, true>(wide_out, c, plan, mid, out, grid, st);
             return;
         }
     }
-    {
-        if (which & 1) k_dct_rows<L, LE, false, false, false><<<grid, TP, 0, st>>>(in, mid, plan->d_consts_f64, c->qb.d_tw_f64, c->qb.d_mod, c->k);
-        if (which & 2) k_dct_cols<L, LE, false, false><<<grid, TP, 0, st>>>(mid, out, plan->d_consts_f64, plan->d_consts_pair, c->qb.d_itw_f64, c->qb.d_mod, c->k);
-    }
+    if (which & 1) launch_rows<L, LE, false, false, false>(wide_in, c, plan, in, mid, grid, st);
+    if (which & 2) launch_cols<L, LE, false, false>(wide_out, c, plan, mid, out, grid, st);
 }
 
 int fhe_dct_f64_launch(const fhe_ctx *c, const fhe_dct_plan *plan, const u64 *in, u64 *out, u64 n_blocks, double *mid, hipStream_t st, int which) {
@@ -890,11 +1033,16 @@ int fhe_dct_f64_launch(const fhe_ctx *c, const fhe_dct_plan *plan, const u64 *in
         if (timed_out) return fail(FHE_ERR_HIP, "one-launch experiment: a column workgroup timed out waiting for its row transforms; the output is incomplete");
         return FHE_OK;
     }
+    // the wide kernels move 16 bytes per lane to and from the public ciphertexts, and every offset inside a block is a multiple
+    // of 16: they need `in` and `out` on 16-byte boundaries.  The C ABI promises 8, so a call with either pointer only 8-byte
+    // aligned runs the 8-byte kernels -- it is neither refused nor run wide.  FHE_DCT_WIDE_IO: bit 0 inputs, bit 1 outputs.
+    const bool aligned = !(((uintptr_t)in | (uintptr_t)out) & 15);
+    const bool wi = aligned && (c->opt.dct_wide_io & 1), wo = aligned && (c->opt.dct_wide_io & 2);
     switch (c->logn) {   // LE = 3 is only built for the headline size
-        case 10: launch_pair<10, 4>(c, plan, in, out, mid, (unsigned)grid, big, st, which); break;
-        case 11: launch_pair<11, 3>(c, plan, in, out, mid, (unsigned)grid, big, st, which); break;
-        case 12: if (dct_shape_le(c) == 3) launch_pair<12, 3>(c, plan, in, out, mid, (unsigned)grid, false, st, which); else launch_pair<12, 4>(c, plan, in, out, mid, (unsigned)grid, big, st, which); break;
-        case 13: if (dct_shape_le(c) == 3) launch_pair<13, 3>(c, plan, in, out, mid, (unsigned)grid, big, st, which); else launch_pair<13, 4>(c, plan, in, out, mid, (unsigned)grid, big, st, which); break;
+        case 10: launch_pair<10, 4>(c, plan, in, out, mid, (unsigned)grid, big, st, which, wi, wo); break;
+        case 11: launch_pair<11, 3>(c, plan, in, out, mid, (unsigned)grid, big, st, which, wi, wo); break;
+        case 12: if (dct_shape_le(c) == 3) launch_pair<12, 3>(c, plan, in, out, mid, (unsigned)grid, false, st, which, wi, wo); else launch_pair<12, 4>(c, plan, in, out, mid, (unsigned)grid, big, st, which, wi, wo); break;
+        case 13: if (dct_shape_le(c) == 3) launch_pair<13, 3>(c, plan, in, out, mid, (unsigned)grid, big, st, which, wi, wo); else launch_pair<13, 4>(c, plan, in, out, mid, (unsigned)grid, big, st, which, wi, wo); break;
         default: return fail(FHE_ERR_PARAM, "fused FP64 path supports n in {1024, 2048, 4096, 8192}");
     }
     KERNEL_CHECK();

@@ -242,6 +242,7 @@ static int ctx_create(uint32_t n, const uint64_t *q, uint32_t k, uint64_t t, int
         if (const char *e = getenv("FHE_DCT_LE")) o.dct_le = atoi(e) == 4 ? 4 : 3;
         o.dct_pack = !off("FHE_DCT_PACK");
         o.dct_ldsc = !off("FHE_DCT_LDSC");
+        if (const char *e = getenv("FHE_DCT_WIDE_IO")) { if (e[0] >= '0' && e[0] <= '3' && !e[1]) o.dct_wide_io = (u32)(e[0] - '0'); }
         o.dct_u64_fused = !off("FHE_DCT_U64_FUSED");
         if (const char *e = getenv("FHE_DCT_ONE_LAUNCH")) o.dct_one_launch = (u32)atoi(e);
         o.relin_fused = env_on("FHE_RELIN_FUSED");

@@ -73,6 +73,19 @@ __device__ __forceinline__ f64x2 gld_f64x2(gwin_t w, u32 voff, u32 soff) { retur
 __device__ __forceinline__ void gst_f64x2(gwin_t w, u32 voff, u32 soff, double a, double b) {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f64x2{a, b}), w, voff, soff, 0);
 }
+// two neighbouring u64 coefficients of a public ciphertext (the paired pass-0 layout, dct_fused.hip)
+struct u64x2 { u64 a, b; };
+__device__ __forceinline__ u64x2 gld_u64x2(gwin_t w, u32 voff, u32 soff) { return __builtin_bit_cast(u64x2, __builtin_amdgcn_raw_buffer_load_b128(w, voff, soff, 0)); }
+// The store reads its four data registers over several cycles.  Where a series of these stores shares one register
+// quadruple, hipcc puts the VALU instruction that forms the next value directly behind the store (it inserts no wait
+// state when the offset is in an SGPR), and on gfx950 the store was measured to pick up that next value in a few lanes, once
+// in some hundred launches (profiles/EXPERIMENTS.md section 23).  The `s_nop 1` reads the data registers, so they stay
+// live across it and nothing overwrites them within two wait states of the store.
+__device__ __forceinline__ void gst_u64x2(gwin_t w, u32 voff, u32 soff, u64 a, u64 b) {
+    const u32x4 v = __builtin_bit_cast(u32x4, u64x2{a, b});
+    __builtin_amdgcn_raw_buffer_store_b128(v, w, voff, soff, 0);
+    asm volatile("s_nop 1" ::"v"(v) : "memory");
+}
 
 // Even / odd half of one LL&M line (homo/fhe_image.h:215-242) on a single NTT slot.
 // In:  even: x[m] = d_m + d_(7-m) (tmp0..tmp3);  odd: x[m] = d_m - d_(7-m) (tmp7,tmp6,tmp5,tmp4).

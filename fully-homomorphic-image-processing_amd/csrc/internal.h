@@ -50,6 +50,7 @@ struct FheOptions {
     int dct_le = 3;                  // FHE_DCT_LE=4: 16 coefficients per thread in the fused FP64 pair where 8 is the default
     bool dct_pack = true;            // FHE_DCT_PACK=0: FP64 intermediate instead of the packed one (primes <= 37 bits)
     bool dct_ldsc = true;            // FHE_DCT_LDSC=0: row-kernel constants through registers instead of LDS
+    u32 dct_wide_io = 3;             // FHE_DCT_WIDE_IO=0: the fused FP64 pair reads and writes the public ciphertexts 8 bytes per lane everywhere (1: wide inputs only, 2: wide outputs only)
     bool dct_u64_fused = true;       // FHE_DCT_U64_FUSED=0: three-launch general path instead of the fused u64 pair
     u32 dct_one_launch = 0;          // FHE_DCT_ONE_LAUNCH=D (experiment): rows and columns of the FP64 pair in one launch, columns D units behind the rows
     bool ntt_nolazy = false;         // FHE_NTT_NOLAZY=1: Harvey butterflies with conditional subtractions everywhere
