@@ -98,6 +98,10 @@ SIGNATURES = {
     "fhe_plane_map_plan_info": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u64), C.POINTER(_u32)]),
     "fhe_plane_map": (_i, [_vp, _vp, _vp, _vp, _u32, _u64, _vp]),
     "fhe_mod_switch": (_i, [_vp, _u32, _vp, _vp, _u64, _vp]),
+    "fhe_ksk_sp_words": (_sz, [_vp]),
+    "fhe_key_switch_sp_scratch_bytes": (_sz, [_vp, _u64]),
+    "fhe_relinearize_sp_poly": (_i, [_vp, _vp, _u64, _u32, _vp, _u64, _u64, _vp, _vp, _sz, _vp]),
+    "fhe_apply_galois_sp": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u32, _vp, _vp, _sz, _vp]),
     "fhe_dct_plan_create": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(_vp)]),
     "fhe_dct_plan_destroy": (_i, [_vp]),
     "fhe_dct8x8_scratch_bytes": (_sz, [_vp, _u64]),

@@ -872,6 +872,29 @@ def mod_switch_budget(ctx, budget_bits, k_out, size=2):
     return math.log2(total.denominator) - math.log2(total.numerator)
 
 
+def special_key_switch_budget(ctx, budget_bits, noise_bound=None):
+    """Lower bound (bits, float) on the invariant noise budget after ONE key switch with a special prime (Evaluator.relinearize_sp step,
+    apply_galois with SpecialGaloisKeys), from the budget before.  `ctx` is the PARENT context: its last prime p is the special prime, the
+    ciphertext lives on the first L = k - 1 primes, Q their product.  The switch adds sum_i d_i e_i / p (d_i a residue polynomial below q_i,
+    e_i a key's noise polynomial, n terms per coefficient) and the rounding of the division by p (1/2 per coefficient of u_0, and of u_1
+    times the ternary secret):
+        E = n B sum_(i < L) (q_i - 1) / p + (1 + n) / 2,        B_after >= -log2(2^-B_before + 2 t E / Q).
+    B = noise_bound, the largest absolute value of a key's noise sample; None: what KeyGenerator's sampler can return.  Pure Python on
+    ctx.n, ctx.t, ctx.q, as mod_switch_budget."""
+    from fractions import Fraction
+    q, n = [int(x) for x in ctx.q], int(ctx.n)
+    if len(q) < 2:
+        raise ValueError("special_key_switch_budget: a context of %d prime(s); the last of at least 2 is the special prime" % len(q))
+    if noise_bound is None:
+        from .keys import _Sampler
+        noise_bound = _Sampler.NOISE_MAX
+    p, Q = q[-1], math.prod(q[:-1])
+    E = Fraction(n * int(noise_bound) * sum(qi - 1 for qi in q[:-1]), p) + Fraction(1 + n, 2)
+    total = Fraction(1, 1 << int(budget_bits)) if float(budget_bits) == int(budget_bits) else Fraction(2.0 ** -float(budget_bits))
+    total += 2 * int(ctx.t) * E / Q
+    return math.log2(total.denominator) - math.log2(total.numerator)
+
+
 def mod_switch_primes(ctx, budget_bits, keep_bits, size=2):
     """The smallest k_out whose mod_switch_budget is at least keep_bits; ctx.k (no switch) when not even one drop qualifies."""
     k = len(ctx.q)

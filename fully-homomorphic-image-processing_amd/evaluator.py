@@ -416,6 +416,23 @@ def check_evaluation_keys(ctx, evk_ntt, dbc, need, who):
                          % (who, tuple(evk_ntt.shape), dbc, ctx.k, nd, ctx.n))
 
 
+def check_special_keys(ctx, parent, key, need, who):
+    """The same for the special-prime key switch (fhe_relinearize_sp_poly / fhe_apply_galois_sp): `ctx` is the context the ciphertexts live in,
+    `parent` the one the keys were generated in.  ctx must be parent's first k - 1 primes with its n, t and device, and the tensor must hold
+    `need` key sets of [k - 1][2][k][n] words -- the library reads fhe_ksk_sp_words(parent) words per set behind a bare pointer."""
+    if parent.k < 2:
+        raise ValueError("%s: the keys' context has %d prime(s); a special-prime key switch needs at least 2" % (who, parent.k))
+    if (parent.n, parent.t, parent.device) != (ctx.n, ctx.t, ctx.device) or list(parent.q[:-1]) != list(ctx.q):
+        raise ValueError("%s: special-prime keys of another parent context (n = %d, t = %d, k = %d on %s); the ciphertexts' context must be its "
+                         "first k - 1 primes (this one has n = %d, t = %d, k = %d on %s)" % (who, parent.n, parent.t, parent.k, parent.device, ctx.n, ctx.t, ctx.k, ctx.device))
+    if not isinstance(key, torch.Tensor) or key.dtype != torch.int64 or not key.is_contiguous() or key.device != ctx.device:
+        raise ValueError("%s: special-prime keys must be a contiguous int64 tensor on the context's device" % who)
+    shape = (parent.k - 1, 2, parent.k, parent.n)
+    if key.dim() < 4 or tuple(key.shape[-4:]) != shape or key.numel() < need * int(_lib.load().fhe_ksk_sp_words(parent.h)):
+        raise ValueError("%s: %d special-prime key set(s) of shape [k - 1 = %d][2][k = %d][n = %d] expected, got a tensor of shape %r"
+                         % ((who, need) + shape[:1] + shape[2:] + (tuple(key.shape),)))
+
+
 class Evaluator:
     """seal::Evaluator over batches.  In-place semantics of SEAL are expressed functionally:
     every method returns a new tensor unless `out=` is given (which may alias an input)."""
@@ -588,6 +605,34 @@ class Evaluator:
         _lib.call("fhe_relinearize_n", self.ctx.h, _ptr(work), size, size * kn, _ptr(out), 2 * kn, count, _ptr(evk_ntt), dbc, _ptr(scr), nbytes, _stream())
         return out
 
+    def relinearize_sp(self, a, keys, parent):
+        """relinearize with special-prime keys (fhe_relinearize_sp_poly): this evaluator's context is parent.level(parent.k - 1), `a` a batch of
+        ciphertexts of any size >= 2 over its primes, keys = KeyGenerator(parent).generate_special_evaluation_keys(size - 2)
+        ([size - 2][k - 1][2][k][n]: the keys for s^2 .. s^(size-1)).  One key switch per polynomial above the second, the top one first."""
+        ctx = self.ctx
+        if a.dim() < 3 or tuple(a.shape[-2:]) != (ctx.k, ctx.n) or a.dtype != torch.int64 or a.device != ctx.device:
+            raise ValueError("relinearize_sp: ciphertexts [..., size, k, n] = [..., size, %d, %d] of this context only, got %r" % (ctx.k, ctx.n, tuple(a.shape)))
+        size = a.shape[-3]
+        if size == 2:
+            return a
+        have = keys.shape[0] if isinstance(keys, torch.Tensor) and keys.dim() == 5 else 1
+        if have < size - 2:
+            raise ValueError("relinearize_sp: a ciphertext of %d polynomials needs the keys for s^2 .. s^%d (got %d key set(s))" % (size, size - 1, have))
+        check_special_keys(ctx, parent, keys, size - 2, "relinearize_sp")
+        kn = ctx.k * ctx.n
+        work = a.contiguous().clone()                      # the steps above the last one run in place
+        count = work.numel() // (size * kn)
+        out = torch.empty(tuple(a.shape[:-3]) + (2, ctx.k, ctx.n), dtype=a.dtype, device=a.device)
+        nbytes = _lib.load().fhe_key_switch_sp_scratch_bytes(parent.h, count)
+        scr = self._scratch_buf(nbytes)
+        kw = int(_lib.load().fhe_ksk_sp_words(parent.h))
+        flat = keys.reshape(-1)
+        for p in range(size - 1, 1, -1):
+            last = p == 2
+            _lib.call("fhe_relinearize_sp_poly", parent.h, _ptr(work), size * kn, p, _ptr(out if last else work), 2 * kn if last else size * kn, count,
+                      _ptr(flat[(p - 2) * kw:(p - 1) * kw]), _ptr(scr), nbytes, _stream())
+        return out
+
     # -- seal::Evaluator::rotate_rows / rotate_columns (include/fhe_hip.h: batched slots and Galois rotations) --------
     def _galois_key(self, keys, g, who):
         """the key tensor for element g, refused when the key set belongs to a context of other shapes (the library would read it with
@@ -601,19 +646,31 @@ class Evaluator:
         return key
 
     def apply_galois(self, a, g, keys, out=None):
-        """sigma_g on a batch of size-2 ciphertexts followed by the key switch back to s (fhe_apply_galois): keys = GaloisKeys holding g.
-        `out` may be `a` itself (in place) or a contiguous tensor of the same shape that does not overlap it."""
+        """sigma_g on a batch of size-2 ciphertexts followed by the key switch back to s (fhe_apply_galois): keys = GaloisKeys holding g,
+        or SpecialGaloisKeys of the parent context whose first k - 1 primes are this context's (fhe_apply_galois_sp: the key switch with
+        a special prime).  `out` may be `a` itself (in place) or a contiguous tensor of the same shape that does not overlap it."""
         g = int(g)
         if a.dim() < 3 or a.shape[-3] != 2 or tuple(a.shape[-2:]) != (self.ctx.k, self.ctx.n):
             raise ValueError("apply_galois: ciphertexts of size 2 of this context only (SEAL 2.3 refuses other sizes: relinearize first), got %r" % (tuple(a.shape),))
         if not (g & 1) or not 1 < g < 2 * self.ctx.n:
             raise ValueError("apply_galois: Galois element %d must be odd and in (1, 2n = %d)" % (g, 2 * self.ctx.n))
-        key = self._galois_key(keys, g, "apply_galois")
+        from .keys import SpecialGaloisKeys                # keys.py imports this module
+        special = isinstance(keys, SpecialGaloisKeys)      # keys.ctx is then the PARENT context, this one its first k - 1 primes
+        if special:
+            key = keys.key(g)
+            check_special_keys(self.ctx, keys.ctx, key, 1, "apply_galois")
+        else:
+            key = self._galois_key(keys, g, "apply_galois")
         if out is not None and (tuple(out.shape) != tuple(a.shape) or out.dtype != a.dtype or not out.is_contiguous() or out.device != a.device):
             raise ValueError("apply_galois: `out` must be a contiguous int64 tensor of shape %r on the input's device" % (tuple(a.shape),))
         out = torch.empty_like(a) if out is None else out
         ctw = 2 * self.ctx.k * self.ctx.n
         count = self._npolys(a) // 2
+        if special:
+            nbytes = _lib.load().fhe_key_switch_sp_scratch_bytes(keys.ctx.h, count)
+            scr = self._scratch_buf(nbytes)
+            _lib.call("fhe_apply_galois_sp", keys.ctx.h, _ptr(a), ctw, _ptr(out), ctw, count, g, _ptr(key), _ptr(scr), nbytes, _stream())
+            return out
         nbytes = _lib.load().fhe_apply_galois_scratch_bytes(self.ctx.h, keys.dbc, count)
         scr = self._scratch_buf(nbytes)
         _lib.call("fhe_apply_galois", self.ctx.h, _ptr(a), ctw, _ptr(out), ctw, count, g, _ptr(key), keys.dbc, _ptr(scr), nbytes, _stream())

@@ -50,6 +50,8 @@ class _Sampler:
     """seed=None (the default): every draw comes from the OS CSPRNG.  An explicit seed selects a
     reproducible numpy PCG64 stream -- tests only; never pass a seed for keys that protect data."""
 
+    NOISE_MAX = 19          # largest |e| noise() returns: the normal of sigma 3.19 clipped at 6 sigma (circuits.special_key_switch_budget reads it)
+
     def __init__(self, ctx, seed=None):
         self.ctx = ctx
         self.rng = _OsRandom() if seed is None else np.random.default_rng(seed)
@@ -61,10 +63,10 @@ class _Sampler:
     def noise(self):
         n = self.ctx.n
         e = np.rint(self.rng.normal(0.0, 3.19, size=n))
-        bad = np.abs(e) > 19
+        bad = np.abs(e) > self.NOISE_MAX
         while bad.any():                                   # clipped at 6 sigma
             e[bad] = np.rint(self.rng.normal(0.0, 3.19, size=int(bad.sum())))
-            bad = np.abs(e) > 19
+            bad = np.abs(e) > self.NOISE_MAX
         e = e.astype(np.int64)
         return np.stack([np.where(e < 0, q + e, e).astype(np.uint64) for q in self.ctx.q])
 
@@ -172,6 +174,61 @@ class KeyGenerator:
             keys[g] = self._switch_key(apply_galois_host(sk, g, ctx.q), dbc)
         return GaloisKeys(ctx, dbc, keys)
 
+    # -- keys for the key switch with a special prime (include/fhe_hip.h: fhe_relinearize_sp_poly / fhe_apply_galois_sp) --------
+    def _switch_key_special(self, target):
+        """[k - 1][2][k][n] in NTT form: the key that switches a polynomial multiplying `target` ([k, n] host residues over ALL k primes,
+        coefficient form) back to s when the LAST prime p of this context is the special prime: entry i = (-(a s + e) + (p mod q_i) target on
+        component i only, a) -- _switch_key's form with the factor 2^(dbc d) replaced by p mod q_i, no digit index and rows i < k - 1 only"""
+        ctx = self.ctx
+        if ctx.k < 2:
+            raise ValueError("special-prime keys need a context of at least 2 primes (the last one is the special prime)")
+        p = ctx.q[-1]
+        key = np.zeros((ctx.k - 1, 2, ctx.k, ctx.n), dtype=np.uint64)
+        for i in range(ctx.k - 1):
+            a = self._smp.uniform()
+            e = to_device(self._smp.noise()[None], ctx.device)
+            k0 = _ring_mul(ctx, to_device(a[None], ctx.device), self._sk_ntt)
+            _lib.call("fhe_add", ctx.h, _ptr(k0), _ptr(e), _ptr(k0), 1, _stream())
+            _lib.call("fhe_negate", ctx.h, _ptr(k0), _ptr(k0), 1, _stream())
+            h0 = to_host(k0)[0].copy()
+            qi = ctx.q[i]
+            f = p % qi
+            h0[i] = np.array([(int(x) + int(s) * f) % qi for x, s in zip(h0[i], target[i])], dtype=np.uint64)
+            key[i, 0], key[i, 1] = h0, a
+        return _ntt(ctx, to_device(key, ctx.device))
+
+    def generate_special_evaluation_keys(self, count=1):
+        """[count][k - 1][2][k][n], NTT form: the keys for s^2 .. s^(count+1) of Evaluator(ctx.level(k - 1)).relinearize_sp, which takes a
+        ciphertext of count + 2 polynomials over the first k - 1 primes down to 2"""
+        ctx = self.ctx
+        if ctx.k < 2:
+            raise ValueError("special-prime keys need a context of at least 2 primes (the last one is the special prime)")
+        out = []
+        power = self._sk
+        for _ in range(int(count)):
+            power = _ring_mul(ctx, power, self._sk_ntt)
+            out.append(self._switch_key_special(to_host(power)[0]))
+        return torch.stack(out).contiguous()
+
+    def generate_special_galois_keys(self, elements=None):
+        """SpecialGaloisKeys: one special-prime key per Galois element g, for the target sigma_g(s); elements=None: the set of
+        generate_galois_keys.  Evaluator(ctx.level(k - 1)).apply_galois / rotate_rows / rotate_columns take them in place of GaloisKeys."""
+        ctx = self.ctx
+        if ctx.k < 2:
+            raise ValueError("special-prime keys need a context of at least 2 primes (the last one is the special prime)")
+        if elements is None:
+            elements = default_galois_elements(ctx.n)
+        sk = to_host(self._sk)[0]
+        keys = {}
+        for g in elements:
+            g = int(g)
+            if g in keys:
+                continue
+            if not (g & 1) or not 1 < g < 2 * ctx.n:
+                raise ValueError("Galois element %d: must be odd and in (1, 2n = %d)" % (g, 2 * ctx.n))
+            keys[g] = self._switch_key_special(apply_galois_host(sk, g, ctx.q))
+        return SpecialGaloisKeys(ctx, keys)
+
 
 def galois_element(n, steps=0, swap_rows=False):
     """the Galois element of a row rotation LEFT by `steps` slots (negative: right), times 2n - 1 with swap_rows (fhe_galois_element)"""
@@ -222,6 +279,25 @@ class GaloisKeys:
         for g in self.elements():
             f.write(struct.pack("<2I", g, 0))
             f.write(to_host(self._keys[g]).tobytes())
+
+    def key(self, g):
+        if int(g) not in self._keys:
+            raise ValueError("no Galois key for element %d (have %r)" % (g, self.elements()))
+        return self._keys[int(g)]
+
+
+class SpecialGaloisKeys:
+    """Galois element -> special-prime key-switching key (device tensor [k - 1][2][k][n], NTT form).  `ctx` is the PARENT context, of k
+    primes, in which the keys were generated; the ciphertexts they rotate live in ctx.level(k - 1)."""
+
+    def __init__(self, ctx, keys):
+        self.ctx, self._keys = ctx, dict(keys)
+
+    def has(self, g):
+        return int(g) in self._keys
+
+    def elements(self):
+        return sorted(self._keys)
 
     def key(self, g):
         if int(g) not in self._keys:

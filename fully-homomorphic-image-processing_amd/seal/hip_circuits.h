@@ -15,6 +15,9 @@
 //   plane_map
 //   seal::hip::level_context,    modulus switching (fhe_mod_switch): a batch goes from the context's k primes to its first k_out, into the
 //   mod_switch                   level context, where it decrypts under the same secret key restricted to those primes
+//   seal::hip::SpecialKeys,      key switching with a special prime (fhe_relinearize_sp_poly / fhe_apply_galois_sp), evaluation side: batches of the
+//   SpecialGaloisKeys,           level context of k - 1 primes, key tensors made by the Python host's key generator in the context of k primes
+//   relinearize_sp, apply_galois_sp, rotate_rows_sp, rotate_columns_sp
 //
 // (The slot encoder and the Galois rotations -- seal::hip::batch_encode / batch_decode, GaloisKeys, generate_galois_keys, apply_galois,
 // rotate_rows, rotate_columns -- work on std::vector<seal::Ciphertext> and live in seal/seal.h, beside filter2d and remap.)
@@ -493,6 +496,98 @@ inline CiphertextBatch mod_switch(const SEALContext &ctx, const SEALContext &lev
     CiphertextBatch out(level, in.count(), in.size());
     detail::check(fhe_mod_switch(s.h, l.k, in.ptr(), out.ptr(), (uint64_t)in.count() * in.size(), nullptr), "mod_switch");
     return out;
+}
+
+// ---- key switching with a special prime (include/fhe_hip.h: fhe_relinearize_sp_poly / fhe_apply_galois_sp), evaluation side ------------
+// `parent` has k primes, the last one the special prime; the batches belong to `level` = level_context(parent, k - 1).  The keys come from
+// the caller (the Python host's KeyGenerator.generate_special_evaluation_keys / generate_special_galois_keys): words in the library's NTT
+// form, [sets][k - 1][2][k][n].
+class SpecialKeys {
+public:
+    SpecialKeys() : sets_(0) {}
+    // host words of `sets` key sets of `parent`
+    SpecialKeys(const SEALContext &parent, const std::vector<uint64_t> &words, size_t sets) : sets_(sets) {
+        const size_t kw = fhe_ksk_sp_words(parent.state()->h);
+        if (!kw || words.size() != sets * kw) throw std::invalid_argument("SpecialKeys: the words do not hold that many key sets of this context");
+        buf_.resize(words.size());
+        if (!words.empty()) buf_.upload(words.data(), words.size());
+    }
+    size_t sets() const { return sets_; }
+    const uint64_t *set(const SEALContext &parent, size_t i) const {
+        const size_t kw = fhe_ksk_sp_words(parent.state()->h);
+        if (i >= sets_ || buf_.words() != sets_ * kw) throw std::invalid_argument("SpecialKeys: no such key set for this context");
+        return buf_.ptr() + i * kw;
+    }
+private:
+    detail::DevBuf buf_;
+    size_t sets_;
+};
+class SpecialGaloisKeys {
+public:
+    void add(uint32_t g, SpecialKeys key) { keys_[g] = std::move(key); }
+    bool has(uint32_t g) const { return keys_.count(g) != 0; }
+    const uint64_t *key(const SEALContext &parent, uint32_t g) const {
+        std::map<uint32_t, SpecialKeys>::const_iterator it = keys_.find(g);
+        if (it == keys_.end()) throw std::invalid_argument("no special-prime Galois key for this element");
+        return it->second.set(parent, 0);
+    }
+private:
+    std::map<uint32_t, SpecialKeys> keys_;
+};
+inline void check_special_level(const SEALContext &parent, const SEALContext &level, const CiphertextBatch &b, const char *who) {
+    const detail::CtxState &s = *parent.state(), &l = *level.state();
+    if (s.k < 2 || l.n != s.n || l.t != s.t || l.k + 1 != s.k || !std::equal(l.q.begin(), l.q.end(), s.q.begin()))
+        throw std::invalid_argument(std::string(who) + ": `level` is not the context of the parent's first k - 1 primes");
+    if (!b.of(level)) throw std::invalid_argument(std::string(who) + ": the batch does not belong to the level context");
+}
+
+// evaluator.relinearize with special-prime keys: any size >= 3 down to 2, the top polynomial first; keys: the sets for s^2 .. s^(size-1)
+inline CiphertextBatch relinearize_sp(const SEALContext &parent, const SEALContext &level, const CiphertextBatch &in, const SpecialKeys &keys) {
+    check_special_level(parent, level, in, "relinearize_sp");
+    const detail::CtxState &s = *parent.state();
+    const uint32_t size = in.size();
+    if (size < 3) throw std::invalid_argument("relinearize_sp: ciphertexts of at least 3 polynomials");
+    if (keys.sets() < size - 2) throw std::invalid_argument("relinearize_sp: not enough key sets for a ciphertext of this size");
+    CiphertextBatch out(level, in.count(), 2);
+    if (!in.count()) return out;
+    CiphertextBatch work = in;                                            // the steps above the last one run in place
+    const size_t bytes = fhe_key_switch_sp_scratch_bytes(s.h, in.count());
+    detail::DevBuf scratch((bytes + 7) / 8 + 1);
+    for (uint32_t p = size - 1; p >= 2; --p) {
+        const bool last = p == 2;
+        detail::check(fhe_relinearize_sp_poly(s.h, work.ptr(), work.ct_words(), p, last ? out.ptr() : work.ptr(), last ? out.ct_words() : work.ct_words(), in.count(),
+                                              keys.set(parent, p - 2), scratch.ptr(), bytes, nullptr), "relinearize_sp");
+    }
+    detail::check(fhe_stream_sync(nullptr), "sync");
+    return out;
+}
+// Evaluator::apply_galois on a batch of size-2 ciphertexts of `level`, in place
+inline void apply_galois_sp(const SEALContext &parent, const SEALContext &level, CiphertextBatch &cts, uint32_t g, const SpecialGaloisKeys &keys) {
+    check_special_level(parent, level, cts, "apply_galois_sp");
+    const detail::CtxState &s = *parent.state();
+    if (cts.count() && cts.size() != 2) throw std::invalid_argument("apply_galois_sp needs size-2 ciphertexts (relinearize first)");
+    const uint64_t *key = keys.key(parent, g);
+    if (!cts.count()) return;
+    const size_t bytes = fhe_key_switch_sp_scratch_bytes(s.h, cts.count());
+    detail::DevBuf scratch((bytes + 7) / 8 + 1);
+    detail::check(fhe_apply_galois_sp(s.h, cts.ptr(), cts.ct_words(), cts.ptr(), cts.ct_words(), cts.count(), g, key, scratch.ptr(), bytes, nullptr), "apply_galois_sp");
+    detail::check(fhe_stream_sync(nullptr), "sync");
+}
+// rotate_rows / rotate_columns of seal/seal.h with special-prime keys: the same reduction of `steps` and the same hops
+inline void rotate_rows_sp(const SEALContext &parent, const SEALContext &level, CiphertextBatch &cts, int steps, const SpecialGaloisKeys &keys) {
+    const int half = (int)(parent.state()->n / 2);
+    int r = steps % half;
+    if (r < 0) r += half;
+    if (r > half / 2) r -= half;
+    if (r == 0) return;
+    const uint32_t g = galois_element(parent, r);
+    if (keys.has(g)) { apply_galois_sp(parent, level, cts, g, keys); return; }
+    const int sign = r > 0 ? 1 : -1, mag = r > 0 ? r : -r;
+    for (int i = 0; (1 << i) <= mag; ++i)
+        if ((mag >> i) & 1) apply_galois_sp(parent, level, cts, galois_element(parent, sign * (1 << i)), keys);
+}
+inline void rotate_columns_sp(const SEALContext &parent, const SEALContext &level, CiphertextBatch &cts, const SpecialGaloisKeys &keys) {
+    apply_galois_sp(parent, level, cts, 2 * parent.state()->n - 1, keys);
 }
 
 }  // namespace hip

@@ -84,7 +84,8 @@ const char *fhe_last_error(void);
  *      fhe_batch_decode, fhe_galois_element and fhe_apply_galois (batched slots and Galois rotations), and for fhe_block8x8_plan_create /
  *      destroy, fhe_block8x8_scalar, fhe_channel_mix and fhe_dct8_matrix (integer linear maps across slot-packed ciphertexts), and for
  *      fhe_plane_map_plan_create / destroy / info and fhe_plane_map (sparse integer maps across position-packed ciphertexts), and for
- *      fhe_ctx_create_level and fhe_mod_switch (modulus switching: dropping RNS primes from ciphertexts).
+ *      fhe_ctx_create_level and fhe_mod_switch (modulus switching: dropping RNS primes from ciphertexts), and for fhe_ksk_sp_words,
+ *      fhe_key_switch_sp_scratch_bytes, fhe_relinearize_sp_poly and fhe_apply_galois_sp (key switching with a special prime).
  * A host compiled against this header compares fhe_abi_version() with FHE_ABI_VERSION before anything else (the Python
  * binding and seal/seal.h do). */
 #define FHE_ABI_VERSION 4
@@ -422,6 +423,41 @@ int fhe_plane_map(const fhe_ctx *ctx, const fhe_plane_map_plan *plan, const uint
  * Refused (FHE_ERR_PARAM) before anything is enqueued: k_out == 0 or k_out >= k, a null pointer, any overlap of the input and output ranges
  * (the strides differ: there is no in-place form).  n_polys == 0 is a no-op. */
 int fhe_mod_switch(const fhe_ctx *ctx, uint32_t k_out, const uint64_t *in, uint64_t *out, uint64_t n_polys, fhe_stream stream);
+
+/* ---- key switching with a special prime: relinearisation steps and Galois rotations without a digit decomposition ----------------------
+ * The key switches above cut every source residue into digits of dbc bits: k * digits * k forward transforms, and a noise that grows with
+ * 2^dbc.  Here the LAST prime of the context is the special prime p = q_(k-1); ciphertexts live on the first L = k - 1 primes
+ * ([size][L][n], canonical residues: they belong to the context fhe_ctx_create_level(ctx, k - 1) makes and decrypt there under sk[:L]), keys
+ * are made in ctx over all k primes, the key-switch product is formed modulo all k primes and then divided by p with rounding: L * k forward
+ * transforms and 2 k inverse ones, and a noise of a few bits whatever the primes' size.  New entry points only (csrc/keyswitch_sp.hip).
+ *
+ * The key for a target polynomial T (s^j, or sigma_g(s), as residues over all k primes): [L][2][k][n] in NTT form (fhe_ntt_forward of ctx),
+ * fhe_ksk_sp_words(ctx) = L * 2 * k * n words (0 when k < 2); entry i = (-(a_i s + e_i) + P_i T, a_i), a_i uniform, e_i noise, where "+ P_i T"
+ * adds (p mod q_i) * T mod q_i on component i and nothing on any other component, the special prime's included
+ * (P_i = p * (Q / q_i) * [(Q / q_i)^-1]_(q_i) reduced modulo each prime, Q = q_0 .. q_(L-1)).
+ *
+ * KS(d, K) of a source polynomial d [L][n] (coefficient form, canonical), for pp in {0, 1}:
+ *   1. for every r < k:  acc_pp,r = sum_(i < L) [d_i]_(q_r) (*) K_i,pp,r  mod q_r, (*) the negacyclic product and [d_i]_(q_r) the integer
+ *      d_i[c] in [0, q_i) reduced modulo q_r, coefficient by coefficient (not centred; d_i itself for r == i);
+ *   2. u_pp = one drop of fhe_mod_switch, k -> k - 1 primes, applied to acc_pp (bit for bit).
+ * fhe_relinearize_sp_poly (src_poly >= 2):  out = (c_0 + u_0, c_1 + u_1),  u = KS(c_src_poly, the key for s^src_poly); ct is
+ *   [count] ciphertexts of at least src_poly + 1 polynomials.
+ * fhe_apply_galois_sp (g odd in (1, 2n)):   out = (sigma_g(c_0) + u_0, u_1),  u = KS(sigma_g(c_1), the key for sigma_g(s)); sigma_g as above:
+ *   the negation is modulo the SOURCE prime q_i, before the reduction to q_r, and the negation of 0 is 0.
+ * Additions are modulo q_r and fully reduced.  ct at ct_stride_words, out2 [2][L][n] at out_stride_words; out2 either IS the input (same
+ * pointer and stride: in place) or overlaps neither the input nor the scratch (the rule of fhe_relinearize_to).
+ * Noise: one switch adds at most E = n B sum_(i < L) (q_i - 1) / p + (1 + n) / 2 to the numerator of the invariant noise (B the largest
+ * noise sample): budget after >= -log2(2^-before + 2 t E / Q)  (circuits.special_key_switch_budget in the Python host).
+ * Refused (FHE_ERR_PARAM) before anything is enqueued: k < 2, a null pointer, src_poly < 2, g even / 1 / >= 2n, a stride below the
+ * ciphertext size, scratch_bytes < fhe_key_switch_sp_scratch_bytes(ctx, count), a forbidden overlap.  count == 0 is a no-op.  No device
+ * allocation inside a call. */
+size_t fhe_ksk_sp_words(const fhe_ctx *ctx);
+size_t fhe_key_switch_sp_scratch_bytes(const fhe_ctx *ctx, uint64_t count);
+int fhe_relinearize_sp_poly(const fhe_ctx *ctx, const uint64_t *ct, uint64_t ct_stride_words, uint32_t src_poly, uint64_t *out2,
+                            uint64_t out_stride_words, uint64_t count, const uint64_t *d_key_ntt, void *scratch, size_t scratch_bytes,
+                            fhe_stream stream);
+int fhe_apply_galois_sp(const fhe_ctx *ctx, const uint64_t *ct2, uint64_t ct_stride_words, uint64_t *out2, uint64_t out_stride_words,
+                        uint64_t count, uint32_t galois_elt, const uint64_t *d_key_ntt, void *scratch, size_t scratch_bytes, fhe_stream stream);
 
 /* ---- fused block circuit: encrypted_dct (homo/fhe_image.h:196-288) followed by quantize_fhe
  * (homo/fhe_image.h:294-305) on n_blocks independent 8x8 blocks.  in/out: [n_blocks][64][2][k][n].
