@@ -102,6 +102,11 @@ SIGNATURES = {
     "fhe_key_switch_sp_scratch_bytes": (_sz, [_vp, _u64]),
     "fhe_relinearize_sp_poly": (_i, [_vp, _vp, _u64, _u32, _vp, _u64, _u64, _vp, _vp, _sz, _vp]),
     "fhe_apply_galois_sp": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u32, _vp, _vp, _sz, _vp]),
+    "fhe_rotsum_plan_create": (_i, [_vp, _u32, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "fhe_rotsum_plan_destroy": (_i, [_vp]),
+    "fhe_rotsum_scratch_bytes": (_sz, [_vp, _u64, _i]),
+    "fhe_rotate_sum_sp": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _sz, _vp]),
+    "fhe_rotate_each_sp": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _vp, _sz, _vp]),
     "fhe_dct_plan_create": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(_vp)]),
     "fhe_dct_plan_destroy": (_i, [_vp]),
     "fhe_dct8x8_scratch_bytes": (_sz, [_vp, _u64]),

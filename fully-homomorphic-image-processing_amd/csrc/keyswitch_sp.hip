@@ -22,42 +22,13 @@
 // it then writes (relinearise), or takes sigma_g(c_0,r) through LDS AFTER its transform, as k_galois_inv_add_pm does: every global read of
 // the polynomial has landed before the barrier in front of the first store, and no other workgroup writes that polynomial.
 //
-// The index map of sigma_g and reduce64 are galois.hip's (file-local there); they are restated here so that galois.hip stays as it is.
-#include "internal.h"
+// The index map of sigma_g and reduce64 are galois.hip's (file-local there); they are restated in ksp_core.h, which rotsum.hip shares, so
+// that galois.hip stays as it is.
+#include "ksp_core.h"
 
 #include "host_math.h"
 
 namespace {
-
-// per-call constants by value (wave-uniform): every prime with floor(2^64 / q), and for r < L the pair (m = k - 1, r) of ctx->modswitch
-struct KspTab {
-    u64 q[FHE_MAX_K], r64[FHE_MAX_K];
-    ulonglong2 inv[FHE_MAX_K];      // p^-1 mod q_r with its Shoup companion
-    u64 add[FHE_MAX_K];             // (h mod q_r) + the smallest multiple of q_r that is >= p
-    u64 p, h;                       // the special prime, floor(p / 2)
-};
-
-__device__ __forceinline__ u32 gal_src(u32 j, u32 ginv, u32 n, bool &neg) {      // j < n <= 2^14, ginv < 2n: no overflow
-    const u32 s = (j * ginv) & (2 * n - 1);
-    neg = s >= n;
-    return s & (n - 1);
-}
-__device__ __forceinline__ u64 gal_load(const u64 *__restrict__ p, u32 j, u32 ginv, u32 n, u64 q) {
-    bool neg;
-    const u64 v = p[gal_src(j, ginv, n, neg)];
-    return neg ? negmod(v, q) : v;
-}
-__device__ __forceinline__ u64 reduce64(u64 x, u64 q, u64 r64) {   // x mod q for any x < 2^64
-    u64 r = x - __umul64hi(x, r64) * q;
-    r = csub(r, 2 * q);
-    return csub(r, q);
-}
-// one drop of fhe_mod_switch on one coefficient: x = acc_r in [0, q_r), cp = acc_p in [0, p); x + A - rr < 2^63 for primes below 2^61
-__device__ __forceinline__ u64 ksp_drop(u64 x, u64 cp, const KspTab &T, u32 r) {
-    const u64 rr = csub(cp + T.h, T.p);
-    return mul_shoup(x + T.add[r] - rr, T.inv[r].x, T.inv[r].y, T.q[r]);
-}
-inline dim3 grid2(u32 n, u64 rows) { return dim3((n + 255) / 256, (unsigned)(rows < 32768 ? (rows ? rows : 1) : 32768)); }
 
 // ---- general path -------------------------------------------------------------------------------------------------------------------
 // dig [count][L][k][n]: d_i reduced to every q_r; a rotation also stores sigma(c0_i) beside the digits (a block's gathered reads cross other
@@ -224,22 +195,6 @@ __global__ __launch_bounds__(NttShape<L>::TP, 4) void k_ksp_inv_down_add_pm(cons
     store_coeff<L>(x[0], out + c * out_stride + ((u64)pp * Lq + r) * N, tid);
 }
 
-KspTab ksp_tab(const fhe_ctx *c) {
-    KspTab T{};
-    const u32 k = c->k, m = k - 1;
-    for (u32 i = 0; i < k; i++) {
-        T.q[i] = c->qb.primes[i];
-        T.r64[i] = (u64)(((unsigned __int128)1 << 64) / T.q[i]);
-    }
-    for (u32 r = 0; r < m; r++) {
-        T.inv[r] = c->modswitch.inv[m * (m - 1) / 2 + r];
-        T.add[r] = c->modswitch.add[m * (m - 1) / 2 + r];
-    }
-    T.p = T.q[m];
-    T.h = T.p >> 1;
-    return T;
-}
-
 // the pseudo-Mersenne kernels run when the base has a class, the switch is off, the base's own transforms are not the FP64 ones
 // (fhe_qbase_ntt) and the grid of the first kernel fits one launch
 bool ksp_pm_ok(const fhe_ctx *c, u64 count) {
@@ -261,7 +216,7 @@ int key_switch(const fhe_ctx *c, const u64 *ct, u64 stride, u32 src_poly, u32 gi
         const unsigned g1 = (unsigned)(count * Lq * k), g3 = (unsigned)(count * 2), g4 = (unsigned)(count * 2 * Lq);                                   \
         if (gal) k_ksp_fwd_pm<L, CC, true><<<g1, NttShape<L>::TP, 0, st>>>(ct, stride, dig, base, sp_poly, ginv);                                     \
         else k_ksp_fwd_pm<L, CC, false><<<g1, NttShape<L>::TP, 0, st>>>(ct, stride, dig, base, sp_poly, ginv);                                        \
-        k_ksp_accum_pm<CC><<<grid2(n, count * k), 256, 0, st>>>(dig, key, acc, base, n, count);                                                       \
+        k_ksp_accum_pm<CC><<<ksp_grid2(n, count * k), 256, 0, st>>>(dig, key, acc, base, n, count);                                                       \
         k_ksp_inv_sp_pm<L, CC><<<g3, NttShape<L>::TP, 0, st>>>(acc, aux, base);                                                                       \
         if (gal) k_ksp_inv_down_add_pm<L, CC, true><<<g4, NttShape<L>::TP, 0, st>>>(ct, stride, out2, out_stride, acc, aux, base, T, ginv);           \
         else k_ksp_inv_down_add_pm<L, CC, false><<<g4, NttShape<L>::TP, 0, st>>>(ct, stride, out2, out_stride, acc, aux, base, T, ginv);              \
@@ -272,13 +227,13 @@ int key_switch(const fhe_ctx *c, const u64 *ct, u64 stride, u32 src_poly, u32 gi
         return FHE_OK;
     }
     int rc;
-    if (gal) k_ksp_digits<true><<<grid2(n, count * Lq), 256, 0, st>>>(ct, stride, dig, aux, T, k, n, sp_poly, ginv, count);
-    else k_ksp_digits<false><<<grid2(n, count * Lq), 256, 0, st>>>(ct, stride, dig, aux, T, k, n, sp_poly, ginv, count);
+    if (gal) k_ksp_digits<true><<<ksp_grid2(n, count * Lq), 256, 0, st>>>(ct, stride, dig, aux, T, k, n, sp_poly, ginv, count);
+    else k_ksp_digits<false><<<ksp_grid2(n, count * Lq), 256, 0, st>>>(ct, stride, dig, aux, T, k, n, sp_poly, ginv, count);
     if ((rc = fhe_qbase_ntt(false, c, dig, dig, count * Lq, st))) return rc;
-    k_ksp_accum<<<grid2(n, count * k), 256, 0, st>>>(dig, key, acc, c->qb.d_mod, k, n, count);
+    k_ksp_accum<<<ksp_grid2(n, count * k), 256, 0, st>>>(dig, key, acc, c->qb.d_mod, k, n, count);
     if ((rc = fhe_qbase_ntt(true, c, acc, acc, count * 2, st))) return rc;
-    if (gal) k_ksp_down_add<true><<<grid2(n, count * 2 * Lq), 256, 0, st>>>(ct, stride, out2, out_stride, acc, aux, T, k, n, count);
-    else k_ksp_down_add<false><<<grid2(n, count * 2 * Lq), 256, 0, st>>>(ct, stride, out2, out_stride, acc, aux, T, k, n, count);
+    if (gal) k_ksp_down_add<true><<<ksp_grid2(n, count * 2 * Lq), 256, 0, st>>>(ct, stride, out2, out_stride, acc, aux, T, k, n, count);
+    else k_ksp_down_add<false><<<ksp_grid2(n, count * 2 * Lq), 256, 0, st>>>(ct, stride, out2, out_stride, acc, aux, T, k, n, count);
     KERNEL_CHECK();
     return FHE_OK;
 }
@@ -299,6 +254,40 @@ int check_operands(const fhe_ctx *c, const void *ct, u64 stride, u32 in_polys, c
 }
 
 }  // namespace
+
+// the pieces rotsum.hip runs as they are (ksp_core.h)
+bool fhe_ksp_pm_ok(const fhe_ctx *c, u64 count) { return ksp_pm_ok(c, count); }
+int fhe_ksp_forward(const fhe_ctx *c, const u64 *ct, u64 stride, u32 src_poly, u64 *dig, u64 count, hipStream_t st) {
+    const u32 k = c->k, Lq = k - 1, n = c->n;
+    if (ksp_pm_ok(c, count)) {
+        const RnsBase base = c->qb.dev();
+        const unsigned g1 = (unsigned)(count * Lq * k);
+        if (c->qb.pm_class == 1) { DISPATCH_L(c->logn, (k_ksp_fwd_pm<L, PmA, false><<<g1, NttShape<L>::TP, 0, st>>>(ct, stride, dig, base, src_poly, 0))); }
+        else { DISPATCH_L(c->logn, (k_ksp_fwd_pm<L, PmB, false><<<g1, NttShape<L>::TP, 0, st>>>(ct, stride, dig, base, src_poly, 0))); }
+        KERNEL_CHECK();
+        return FHE_OK;
+    }
+    k_ksp_digits<false><<<ksp_grid2(n, count * Lq), 256, 0, st>>>(ct, stride, dig, nullptr, ksp_tab(c), k, n, src_poly, 0, count);
+    KERNEL_CHECK();
+    return fhe_qbase_ntt(false, c, dig, dig, count * Lq, st);
+}
+int fhe_ksp_inv_sp(const fhe_ctx *c, const u64 *acc, u64 *sp, u64 rows, hipStream_t st) {
+    const RnsBase base = c->qb.dev();
+    if (c->qb.pm_class == 1) { DISPATCH_L(c->logn, (k_ksp_inv_sp_pm<L, PmA><<<(unsigned)rows, NttShape<L>::TP, 0, st>>>(acc, sp, base))); }
+    else { DISPATCH_L(c->logn, (k_ksp_inv_sp_pm<L, PmB><<<(unsigned)rows, NttShape<L>::TP, 0, st>>>(acc, sp, base))); }
+    KERNEL_CHECK();
+    return FHE_OK;
+}
+int fhe_ksp_inv_down_add_galois(const fhe_ctx *c, const u64 *ct, u64 stride, u64 *out, u64 out_stride, const u64 *acc, const u64 *sp, u32 ginv, u64 count,
+                                hipStream_t st) {
+    const RnsBase base = c->qb.dev();
+    const KspTab T = ksp_tab(c);
+    const unsigned g4 = (unsigned)(count * 2 * (c->k - 1));
+    if (c->qb.pm_class == 1) { DISPATCH_L(c->logn, (k_ksp_inv_down_add_pm<L, PmA, true><<<g4, NttShape<L>::TP, 0, st>>>(ct, stride, out, out_stride, acc, sp, base, T, ginv))); }
+    else { DISPATCH_L(c->logn, (k_ksp_inv_down_add_pm<L, PmB, true><<<g4, NttShape<L>::TP, 0, st>>>(ct, stride, out, out_stride, acc, sp, base, T, ginv))); }
+    KERNEL_CHECK();
+    return FHE_OK;
+}
 
 extern "C" size_t fhe_ksk_sp_words(const fhe_ctx *c) {
     if (!c || c->k < 2) return 0;

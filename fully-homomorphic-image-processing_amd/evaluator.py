@@ -398,6 +398,67 @@ class PlaneMapPlan:
             self.h = None
 
 
+class RotSumPlan:
+    """The taps of Evaluator.rotate_sum / rotate_each (fhe_rotsum_plan_create: hoisted special-prime rotations of ONE ciphertext).
+    ctx_level: the context the ciphertexts live in, the first k - 1 primes of keys.ctx; keys: SpecialGaloisKeys that hold every element
+    directly (no hops); elements_or_steps: Galois elements (odd, pairwise distinct, 1 = the ciphertext itself, needs no key), or with
+    steps=True row rotations LEFT by that many slots; weights: integers, non-zero modulo t (None: all 1).  The plan keeps the key tensors
+    alive: the library holds their device pointers."""
+
+    MAX_TAPS = 64
+
+    def __init__(self, ctx_level, special_galois_keys, elements_or_steps, weights=None, steps=False):
+        from .keys import SpecialGaloisKeys, galois_element                # keys.py imports this module
+        keys = special_galois_keys
+        if not isinstance(keys, SpecialGaloisKeys):
+            raise ValueError("RotSumPlan: SpecialGaloisKeys expected (KeyGenerator.generate_special_galois_keys), got %s" % type(keys).__name__)
+        n, t = int(ctx_level.n), int(ctx_level.t)
+        elts = [galois_element(n, int(v)) if steps else int(v) for v in elements_or_steps]
+        w = [1] * len(elts) if weights is None else [int(v) for v in np.asarray(weights).reshape(-1)]
+        if not 1 <= len(elts) <= self.MAX_TAPS:
+            raise ValueError("RotSumPlan: %d taps (1 .. %d)" % (len(elts), self.MAX_TAPS))
+        if len(w) != len(elts):
+            raise ValueError("RotSumPlan: %d weights for %d taps" % (len(w), len(elts)))
+        for j, g in enumerate(elts):
+            if not (g & 1) or not 0 < g < 2 * n:
+                raise ValueError("RotSumPlan: Galois element %d must be odd and in [1, 2n = %d)" % (g, 2 * n))
+            if g in elts[:j]:
+                raise ValueError("RotSumPlan: Galois element %d is repeated" % g)
+            if w[j] % t == 0:
+                raise ValueError("RotSumPlan: the weight of tap %d is 0 modulo t" % j)
+        self._keys = []
+        for g in elts:
+            if g == 1:
+                self._keys.append(None)
+                continue
+            if not keys.has(g):
+                raise ValueError("RotSumPlan: no special Galois key for element %d (have %r); the fused call takes no hops" % (g, keys.elements()))
+            key = keys.key(g)
+            check_special_keys(ctx_level, keys.ctx, key, 1, "RotSumPlan")    # the checks apply_galois makes before a bare pointer is handed over
+            self._keys.append(key)
+        self.ctx, self.parent, self.elements = ctx_level, keys.ctx, elts
+        self.weights = [v % t for v in w]
+        e = np.array(elts, dtype=np.uint32)
+        wv = np.array(self.weights, dtype=np.uint64)
+        kp = (C.c_void_p * len(elts))(*[None if k is None else k.data_ptr() for k in self._keys])
+        h = C.c_void_p()
+        torch.cuda.synchronize(ctx_level.device)                             # the keys are complete before the plan's own (null-stream) transform of X
+        _lib.call("fhe_rotsum_plan_create", keys.ctx.h, len(elts), e.ctypes.data_as(C.c_void_p), wv.ctypes.data_as(C.c_void_p), kp, C.byref(h))
+        self.h = h
+
+    def scratch_bytes(self, count, each=False):
+        return int(_lib.load().fhe_rotsum_scratch_bytes(self.h, int(count), int(bool(each))))
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h:
+            try:
+                _lib.load().fhe_rotsum_plan_destroy(h)
+            except Exception:
+                pass
+            self.h = None
+
+
 def check_evaluation_keys(ctx, evk_ntt, dbc, need, who):
     """The library takes the keys as a bare pointer and reads need * fhe_evk_words(ctx, dbc) words behind it (include/fhe_hip.h): the host
     checks that the tensor it hands over holds them -- a key tensor made for another decomposition bit count (fewer digits), another context or
@@ -674,6 +735,42 @@ class Evaluator:
         nbytes = _lib.load().fhe_apply_galois_scratch_bytes(self.ctx.h, keys.dbc, count)
         scr = self._scratch_buf(nbytes)
         _lib.call("fhe_apply_galois", self.ctx.h, _ptr(a), ctw, _ptr(out), ctw, count, g, _ptr(key), keys.dbc, _ptr(scr), nbytes, _stream())
+        return out
+
+    def _rotsum_operand(self, a, plan, who):
+        if not isinstance(plan, RotSumPlan):
+            raise ValueError("%s: a RotSumPlan expected, got %s" % (who, type(plan).__name__))
+        c = plan.ctx
+        if (c.n, c.k, c.t, c.device) != (self.ctx.n, self.ctx.k, self.ctx.t, self.ctx.device) or list(c.q) != list(self.ctx.q):
+            raise ValueError("%s: the plan was made for another context" % who)
+        if a.dim() < 3 or a.shape[-3] != 2 or tuple(a.shape[-2:]) != (self.ctx.k, self.ctx.n):
+            raise ValueError("%s: ciphertexts of size 2 of this context only, got %r" % (who, tuple(a.shape)))
+        return self._npolys(a) // 2
+
+    def rotate_sum(self, a, plan, out=None):
+        """sum over the plan's taps of w_j * sigma_(g_j)(a), key-switched back to s ONCE (fhe_rotate_sum_sp): one set of forward transforms,
+        one accumulation over all taps, one set of inverse transforms and one rounding, whatever the number of taps.  Decrypts to what
+        the composition of apply_galois, multiply_plain by the constant w_j and add decrypts to; the ciphertext bits are its own.
+        `out` may be `a` itself (in place) or a contiguous tensor of the same shape that does not overlap it."""
+        count = self._rotsum_operand(a, plan, "rotate_sum")
+        if out is not None and (tuple(out.shape) != tuple(a.shape) or out.dtype != a.dtype or not out.is_contiguous() or out.device != a.device):
+            raise ValueError("rotate_sum: `out` must be a contiguous int64 tensor of shape %r on the input's device" % (tuple(a.shape),))
+        out = torch.empty_like(a) if out is None else out
+        ctw = 2 * self.ctx.k * self.ctx.n
+        nbytes = plan.scratch_bytes(count)
+        scr = self._scratch_buf(nbytes)
+        _lib.call("fhe_rotate_sum_sp", plan.h, _ptr(a), ctw, _ptr(out), ctw, count, _ptr(scr), nbytes, _stream())
+        return out
+
+    def rotate_each(self, a, plan):
+        """[taps] + a.shape: sigma_(g_j)(a) key-switched back to s for every tap of the plan, the forward transforms shared
+        (fhe_rotate_each_sp; the plan's weights are not used).  What per-slot plaintext weights and baby-step / giant-step maps need."""
+        count = self._rotsum_operand(a, plan, "rotate_each")
+        out = torch.empty((len(plan.elements),) + tuple(a.shape), dtype=a.dtype, device=a.device)
+        ctw = 2 * self.ctx.k * self.ctx.n
+        nbytes = plan.scratch_bytes(count, each=True)
+        scr = self._scratch_buf(nbytes)
+        _lib.call("fhe_rotate_each_sp", plan.h, _ptr(a), ctw, _ptr(out), ctw, count * ctw, count, _ptr(scr), nbytes, _stream())
         return out
 
     def rotation_plan(self, steps, keys):

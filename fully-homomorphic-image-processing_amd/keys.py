@@ -292,6 +292,7 @@ class SpecialGaloisKeys:
 
     def __init__(self, ctx, keys):
         self.ctx, self._keys = ctx, dict(keys)
+        self.plans = {}                 # RotSumPlans made from these keys, by taps (circuits.packed_filter2d(fused=True) makes each once and keeps the latest circuits.PACKED_FILTER_PLANS)
 
     def has(self, g):
         return int(g) in self._keys

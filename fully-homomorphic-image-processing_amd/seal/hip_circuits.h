@@ -18,6 +18,8 @@
 //   seal::hip::SpecialKeys,      key switching with a special prime (fhe_relinearize_sp_poly / fhe_apply_galois_sp), evaluation side: batches of the
 //   SpecialGaloisKeys,           level context of k - 1 primes, key tensors made by the Python host's key generator in the context of k primes
 //   relinearize_sp, apply_galois_sp, rotate_rows_sp, rotate_columns_sp
+//   seal::hip::RotSumPlan,       hoisted special-prime rotations of one ciphertext (fhe_rotate_sum_sp / fhe_rotate_each_sp): a weighted sum of
+//   rotate_sum_sp, rotate_each_sp  rotations with ONE key-switch tail, or the rotations as separate batches with the forward transforms shared
 //
 // (The slot encoder and the Galois rotations -- seal::hip::batch_encode / batch_decode, GaloisKeys, generate_galois_keys, apply_galois,
 // rotate_rows, rotate_columns -- work on std::vector<seal::Ciphertext> and live in seal/seal.h, beside filter2d and remap.)
@@ -588,6 +590,56 @@ inline void rotate_rows_sp(const SEALContext &parent, const SEALContext &level, 
 }
 inline void rotate_columns_sp(const SEALContext &parent, const SEALContext &level, CiphertextBatch &cts, const SpecialGaloisKeys &keys) {
     apply_galois_sp(parent, level, cts, 2 * parent.state()->n - 1, keys);
+}
+
+// ---- hoisted special-prime rotations (include/fhe_hip.h: fhe_rotsum_plan_create, fhe_rotate_sum_sp, fhe_rotate_each_sp) ----------------------
+// The taps of one weighted sum of rotations: Galois elements (odd, pairwise distinct, 1 = the ciphertext itself), integer weights (non-zero
+// modulo t; empty: all 1) and, for every element but 1, its key in `keys` -- directly: the fused call takes no hops.  The plan holds the
+// keys' device pointers: `keys` must outlive it.  The results decrypt to what the composition of apply_galois_sp, multiply_plain by the
+// constant and add decrypts to; the ciphertext bits are their own (include/fhe_hip.h).
+class RotSumPlan {
+public:
+    RotSumPlan(const SEALContext &parent, const SpecialGaloisKeys &keys, const std::vector<uint32_t> &elements, const std::vector<uint64_t> &weights = std::vector<uint64_t>())
+        : h_(nullptr), taps_(elements.size()) {
+        if (!weights.empty() && weights.size() != elements.size()) throw std::invalid_argument("RotSumPlan: one weight per tap");
+        std::vector<const uint64_t *> ptrs(elements.size(), nullptr);
+        for (size_t j = 0; j < elements.size(); ++j)
+            if (elements[j] != 1) ptrs[j] = keys.key(parent, elements[j]);
+        detail::check(fhe_stream_sync(nullptr), "sync");                     // the keys' uploads are complete
+        detail::check(fhe_rotsum_plan_create(parent.state()->h, (uint32_t)elements.size(), elements.data(), weights.empty() ? nullptr : weights.data(),
+                                             ptrs.data(), &h_), "RotSumPlan");
+    }
+    ~RotSumPlan() { fhe_rotsum_plan_destroy(h_); }
+    RotSumPlan(const RotSumPlan &) = delete;
+    RotSumPlan &operator=(const RotSumPlan &) = delete;
+    const fhe_rotsum_plan *handle() const { return h_; }
+    size_t taps() const { return taps_; }
+private:
+    fhe_rotsum_plan *h_;
+    size_t taps_;
+};
+// Evaluator.rotate_sum of the Python host, in place on a batch of size-2 ciphertexts of `level`
+inline void rotate_sum_sp(const SEALContext &parent, const SEALContext &level, CiphertextBatch &cts, const RotSumPlan &plan) {
+    check_special_level(parent, level, cts, "rotate_sum_sp");
+    if (cts.count() && cts.size() != 2) throw std::invalid_argument("rotate_sum_sp needs size-2 ciphertexts (relinearize first)");
+    if (!cts.count()) return;
+    const size_t bytes = fhe_rotsum_scratch_bytes(plan.handle(), cts.count(), 0);
+    detail::DevBuf scratch((bytes + 7) / 8 + 1);
+    detail::check(fhe_rotate_sum_sp(plan.handle(), cts.ptr(), cts.ct_words(), cts.ptr(), cts.ct_words(), cts.count(), scratch.ptr(), bytes, nullptr), "rotate_sum_sp");
+    detail::check(fhe_stream_sync(nullptr), "sync");
+}
+// Evaluator.rotate_each: one batch of plan.taps() * in.count() ciphertexts, tap-major (ciphertext c of tap j is element j * in.count() + c)
+inline CiphertextBatch rotate_each_sp(const SEALContext &parent, const SEALContext &level, const CiphertextBatch &in, const RotSumPlan &plan) {
+    check_special_level(parent, level, in, "rotate_each_sp");
+    if (in.count() && in.size() != 2) throw std::invalid_argument("rotate_each_sp needs size-2 ciphertexts (relinearize first)");
+    CiphertextBatch out(level, plan.taps() * in.count(), 2);
+    if (!in.count()) return out;
+    const size_t bytes = fhe_rotsum_scratch_bytes(plan.handle(), in.count(), 1);
+    detail::DevBuf scratch((bytes + 7) / 8 + 1);
+    detail::check(fhe_rotate_each_sp(plan.handle(), in.ptr(), in.ct_words(), out.ptr(), out.ct_words(), in.count() * out.ct_words(), in.count(), scratch.ptr(), bytes,
+                                     nullptr), "rotate_each_sp");
+    detail::check(fhe_stream_sync(nullptr), "sync");
+    return out;
 }
 
 }  // namespace hip

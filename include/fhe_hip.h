@@ -85,7 +85,9 @@ const char *fhe_last_error(void);
  *      destroy, fhe_block8x8_scalar, fhe_channel_mix and fhe_dct8_matrix (integer linear maps across slot-packed ciphertexts), and for
  *      fhe_plane_map_plan_create / destroy / info and fhe_plane_map (sparse integer maps across position-packed ciphertexts), and for
  *      fhe_ctx_create_level and fhe_mod_switch (modulus switching: dropping RNS primes from ciphertexts), and for fhe_ksk_sp_words,
- *      fhe_key_switch_sp_scratch_bytes, fhe_relinearize_sp_poly and fhe_apply_galois_sp (key switching with a special prime).
+ *      fhe_key_switch_sp_scratch_bytes, fhe_relinearize_sp_poly and fhe_apply_galois_sp (key switching with a special prime), and for
+ *      fhe_rotsum_plan_create / destroy, fhe_rotsum_scratch_bytes, fhe_rotate_sum_sp and fhe_rotate_each_sp (hoisted special-prime
+ *      rotations of one ciphertext and their fused weighted sum).
  * A host compiled against this header compares fhe_abi_version() with FHE_ABI_VERSION before anything else (the Python
  * binding and seal/seal.h do). */
 #define FHE_ABI_VERSION 4
@@ -458,6 +460,45 @@ int fhe_relinearize_sp_poly(const fhe_ctx *ctx, const uint64_t *ct, uint64_t ct_
                             fhe_stream stream);
 int fhe_apply_galois_sp(const fhe_ctx *ctx, const uint64_t *ct2, uint64_t ct_stride_words, uint64_t *out2, uint64_t out_stride_words,
                         uint64_t count, uint32_t galois_elt, const uint64_t *d_key_ntt, void *scratch, size_t scratch_bytes, fhe_stream stream);
+
+/* ---- hoisted special-prime rotations of ONE ciphertext and their fused weighted sum (csrc/rotsum.hip) ---------------------------------------
+ * The setting is the one above: ctx has k >= 2 primes, the last one is the special prime, ciphertexts [2][L][n] live on the first L = k - 1,
+ * keys are [L][2][k][n] in NTT form, the drop is one drop of fhe_mod_switch.  A plan holds G taps, 1 <= G <= 64: pairwise distinct Galois
+ * elements g_j, odd, in [1, 2n) (g = 1: no rotation, no key), weights w_j, non-zero modulo t, with the centred lift w'_j in (-t/2, t/2]
+ * reduced to every q_r (r < k), and K_j, the special Galois key for sigma_(g_j)(s) (a device pointer; ignored, and may be null, for g = 1).
+ * With D_i,r = NTT_(q_r)([c_1,i]_(q_r)) ([.]_(q_r) as above: the integer in [0, q_i) reduced modulo q_r) and pi_g the permutation of NTT slots
+ * with pi_g(NTT(a)) = NTT(sigma_g(a)) in R_(q_r):
+ *   fhe_rotate_sum_sp:   acc_pp,r = sum_(j: g_j != 1) w'_j * sum_(i < L) pi_(g_j)(D_i,r) (*) K_j,i,pp,r  mod q_r   for every r < k,
+ *                        u_pp = one drop (k -> k - 1) of acc_pp, bit for bit,
+ *                        out_0 = u_0 + sum_j w'_j sigma_(g_j)(c_0),    out_1 = u_1 + sum_(j: g_j = 1) w'_j c_1;
+ *   fhe_rotate_each_sp:  out[j] = (sigma_(g_j)(c_0) + u_0^(j), u_1^(j)), acc^(j) the inner sum of tap j alone (w' = 1); out[j] = ct for g_j = 1.
+ *                        Output j of ciphertext c starts at out + j * tap_stride_words + c * out_stride_words.
+ * All results are modulo q_r and fully reduced.  The digit of tap j is the integer polynomial sigma_(g_j)(d_i) taken over Z, coefficients in
+ * (-q_i, q_i), reduced to every q_r: congruent to sigma_g(c_1) modulo q_i, so a valid RNS decomposition of the same magnitude.  It is NOT the
+ * digit of fhe_apply_galois_sp, which negates modulo q_i and THEN reduces to q_r: the two differ by q_i mod q_r at every negated non-zero
+ * coefficient for r != i, so these entry points decrypt to what the composition of fhe_apply_galois_sp, fhe_multiply_plain by the constant w_j
+ * and fhe_add decrypts to, under the noise bound below, but their ciphertext bits are their own.
+ * Noise: the call adds at most E = (sum_j |w'_j|) n B sum_(i < L) (q_i - 1) / p + (1 + n) / 2 to the numerator of the invariant noise (one
+ * rounding, whatever G is) and scales the input's invariant noise by at most W = sum_j |w'_j|.  That factor IS the scalar products' usual
+ * term: an integer scalar commutes with the scaling by t / Q up to multiples of t, so the (Q mod t) m / Q part of the input's invariant noise
+ * grows with the rest of it and nothing is added beside it.  budget after >= -log2(W 2^-before + 2 t E / Q)  (circuits.rotate_sum_budget in
+ * the Python host).
+ * The slot permutations are derived, at plan creation, from the context's own forward transform of the monomial X (slot s holds psi^(e_s);
+ * pi_g reads slot s from the slot holding psi^(e_s g mod 2n)): the NTT-form order stays internal.  weights == NULL: every weight is 1.  The plan keeps the key POINTERS: the keys must stay
+ * where they are while the plan is used.  Plan creation allocates and synchronises; the two calls do neither.
+ * In place: fhe_rotate_sum_sp allows out2 == ct2 with equal strides (the rule of fhe_apply_galois_sp); fhe_rotate_each_sp refuses any overlap.
+ * Refused (FHE_ERR_PARAM) before anything is enqueued: k < 2, G == 0 or G > 64, an element that is even or >= 2n, a repeated element, a
+ * weight that is 0 modulo t, a null key for g != 1, a null pointer, a stride below the ciphertext size (a tap stride below one batch of
+ * outputs), scratch_bytes < fhe_rotsum_scratch_bytes(plan, count, each), a forbidden overlap.  count == 0 is a no-op. */
+typedef struct fhe_rotsum_plan fhe_rotsum_plan;
+int fhe_rotsum_plan_create(const fhe_ctx *ctx, uint32_t taps, const uint32_t *galois_elts, const uint64_t *weights,
+                           const uint64_t *const *d_keys_ntt, fhe_rotsum_plan **out);
+int fhe_rotsum_plan_destroy(fhe_rotsum_plan *plan);
+size_t fhe_rotsum_scratch_bytes(const fhe_rotsum_plan *plan, uint64_t count, int each);
+int fhe_rotate_sum_sp(const fhe_rotsum_plan *plan, const uint64_t *ct2, uint64_t ct_stride_words, uint64_t *out2, uint64_t out_stride_words,
+                      uint64_t count, void *scratch, size_t scratch_bytes, fhe_stream stream);
+int fhe_rotate_each_sp(const fhe_rotsum_plan *plan, const uint64_t *ct2, uint64_t ct_stride_words, uint64_t *out, uint64_t out_stride_words,
+                       uint64_t tap_stride_words, uint64_t count, void *scratch, size_t scratch_bytes, fhe_stream stream);
 
 /* ---- fused block circuit: encrypted_dct (homo/fhe_image.h:196-288) followed by quantize_fhe
  * (homo/fhe_image.h:294-305) on n_blocks independent 8x8 blocks.  in/out: [n_blocks][64][2][k][n].
