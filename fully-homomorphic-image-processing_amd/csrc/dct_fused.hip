@@ -401,29 +401,33 @@ __device__ __forceinline__ void rows_body(const u64 *__restrict__ in, double *__
     if constexpr (WIDE) {
         // paired pass-0 mapping: polynomial 2h + j (= d_(2h+j) +- d_(7-2h-j)), coefficients r*TP + 2u + {0, 1}.  The two
         // ciphertext offsets that depend on h are wave-uniform (pair_half); a wave reads 1 KiB contiguously per instruction.
-        // Staging stays at 32 VGPRs: four rows of a polynomial pair at a time.
+        // Staging stays at 32 VGPRs, and three groups of eight requests are in flight before the first wait instead of one
+        // (in this phase x[][] is not live yet, so its own registers receive half of the loads; profiles/EXPERIMENTS.md 24).
         const u32 h = (u32)pair_half<TP>(tid), vw = 16u * ((u32)tid % (TP / 2));
         const u32 soa = h ? 2u * ctb : 0u, sob = h ? 4u * ctb : 6u * ctb;
+        // Request i = j * E + r is the pair of row r: qa -> x[2j][r], x[2j+1][r].  The two doubles formed from a pair take the
+        // four registers its `a` side arrived in, so all 2E `a` requests cost what x costs anyway; the `b` side goes
+        // through a ring of E quadruples.  Order a0 b0 .. a(E-1) b(E-1) a(E) .. a(2E-1): 3E requests before the first wait.
+        u64x2 qa[2 * E], qb[E];
+        auto lda = [&](int i) { return gld_u64x2(win_in, vw, soa + (u32)(i / E) * ctb + (i % E) * TP * 8); };
+        auto ldb = [&](int i) { return gld_u64x2(win_in, vw, sob + (u32)(1 - i / E) * ctb + (i % E) * TP * 8); };
 #pragma unroll
-        for (int j = 0; j < 2; j++) {
+        for (int i = 0; i < E; i++) {
+            qa[i] = lda(i);
+            qb[i] = ldb(i);
+        }
 #pragma unroll
-            for (int g = 0; g < E / 4; g++) {
-                u64x2 qa[4], qb[4];
+        for (int i = E; i < 2 * E; i++) qa[i] = lda(i);
 #pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    qa[i] = gld_u64x2(win_in, vw, soa + (u32)j * ctb + (4 * g + i) * TP * 8);
-                    qb[i] = gld_u64x2(win_in, vw, sob + (u32)(1 - j) * ctb + (4 * g + i) * TP * 8);
-                }
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    x[2 * j][4 * g + i] = HALF ? u52_biased(qa[i].a) - u52_biased(qb[i].a) : u52_to_f64(qa[i].a + qb[i].a);
-                    x[2 * j + 1][4 * g + i] = HALF ? u52_biased(qa[i].b) - u52_biased(qb[i].b) : u52_to_f64(qa[i].b + qb[i].b);
-                }
-                // the group's values are consumed here, so they are formed (and its 32 staging registers free) before the
-                // next group is requested: a bare fence keeps the loads in order but lets hipcc sink every combine below them
-                asm volatile("" ::"v"(x[2 * j][4 * g]), "v"(x[2 * j][4 * g + 1]), "v"(x[2 * j][4 * g + 2]), "v"(x[2 * j][4 * g + 3]),
-                             "v"(x[2 * j + 1][4 * g]), "v"(x[2 * j + 1][4 * g + 1]), "v"(x[2 * j + 1][4 * g + 2]), "v"(x[2 * j + 1][4 * g + 3]) : "memory");
-            }
+        for (int i = 0; i < 2 * E; i++) {
+            const u64x2 a = qa[i], b = qb[i % E];
+            double &xa = x[2 * (i / E)][i % E], &xb = x[2 * (i / E) + 1][i % E];
+            xa = HALF ? u52_biased(a.a) - u52_biased(b.a) : u52_to_f64(a.a + b.a);
+            xb = HALF ? u52_biased(a.b) - u52_biased(b.b) : u52_to_f64(a.b + b.b);
+            // the pair is consumed here, so it is formed (and its ring slot free) before b(E+i) is requested into that
+            // slot: a bare fence keeps the loads in order but lets hipcc sink every combine below them
+            asm volatile("" ::"v"(xa), "v"(xb) : "memory");
+            if (i < E) qb[i] = ldb(E + i);
         }
     } else if constexpr (LE >= 4) {
         issue(0);
