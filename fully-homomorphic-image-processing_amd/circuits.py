@@ -607,7 +607,7 @@ def packed_filter_taps(n, t, tile_w, weights_int, kw, kh, anchor=None):
     return elts, ws
 
 
-def packed_filter2d(ev, keys, ct, tile_w, weights_int, kw, kh, anchor=None, fused=False):
+def packed_filter2d(ev, keys, ct, tile_w, weights_int, kw, kh, anchor=None, fused=False, border=None):
     """2-D filter with public INTEGER weights over packed tiles: ct [..., 2, k, n] holds, in each row of n/2 slots, a row-major tile of
     tile_w x tile_h pixels.  Output = sum over the taps p = (i, j), row-major over the kernel with x fastest, of
         multiply_plain(rotate_rows(ct, (j - ay) tile_w + (i - ax)), [w_p mod t])
@@ -619,8 +619,26 @@ def packed_filter2d(ev, keys, ct, tile_w, weights_int, kw, kh, anchor=None, fuse
     tap's element directly (no hops: ValueError otherwise); the plan is kept with the keys (`keys.plans`, at most PACKED_FILTER_PLANS of
     them, the oldest dropped first: a sweep over many filters does not pile up device tables).  The same slots modulo t, a budget of at least rotate_sum_budget; the
     ciphertext bits are NOT those of the default path.  Measured faster than the default path in every case tried (box 3x3 and Gauss 5x5
-    at the P8192 and P4096 primes, 256 ciphertexts: 3.2-6.3x)."""
+    at the P8192 and P4096 primes, 256 ciphertexts: 3.2-6.3x).
+    border="zero" | "clamp" (opt-in; None: the paths above, as they are): ONE Evaluator.rotate_diag_sum with packed_filter_diagonals'
+    per-slot weights -- EVERY slot of the tile is the zero-padded / clamp-to-edge filter's value modulo t, the border included
+    (fhe_rotate_diag_sum_sp).  keys: SpecialGaloisKeys that hold every element, the plan is kept as fused=True keeps its
+    own; a budget of at least rotate_diag_budget(plan.plains)."""
     ctx = ev.ctx
+    if border is not None:
+        from .evaluator import RotDiagPlan
+        plans = getattr(keys, "plans", None)
+        ax, ay = filter_anchor(kw, kh) if anchor is None else anchor
+        tag = (tuple(ctx.q), "diag", border, int(tile_w), int(kw), int(kh), int(ax), int(ay), tuple(int(v) % ctx.t for v in np.asarray(weights_int).reshape(-1)))
+        plan = plans.get(tag) if plans is not None else None
+        if plan is None:
+            elts, diags = packed_filter_diagonals(ctx.n, ctx.t, tile_w, weights_int, kw, kh, anchor, border)
+            plan = RotDiagPlan(ctx, keys, elts, diags)
+            if plans is not None:
+                while len(plans) >= PACKED_FILTER_PLANS:
+                    del plans[next(iter(plans))]
+                plans[tag] = plan
+        return ev.rotate_diag_sum(ct, plan)
     if fused:
         from .evaluator import RotSumPlan
         elts, ws = packed_filter_taps(ctx.n, ctx.t, tile_w, weights_int, kw, kh, anchor)
@@ -962,6 +980,134 @@ def rotate_sum_budget(ctx, budget_bits, weights, noise_bound=None):
     if not wc or any(w == 0 for w in wc):
         raise ValueError("rotate_sum_budget: at least one weight, none of them 0 modulo t")
     W = sum(t - w if 2 * w > t else w for w in wc)
+    if noise_bound is None:
+        from .keys import _Sampler
+        noise_bound = _Sampler.NOISE_MAX
+    p, Q = q[-1], math.prod(q[:-1])
+    E = Fraction(W * n * int(noise_bound) * sum(qi - 1 for qi in q[:-1]), p) + Fraction(1 + n, 2)
+    before = Fraction(1, 1 << int(budget_bits)) if float(budget_bits) == int(budget_bits) else Fraction(2.0 ** -float(budget_bits))
+    total = W * before + 2 * t * E / Q
+    return math.log2(total.denominator) - math.log2(total.numerator)
+
+
+def packed_filter_diagonals(n, t, tile_w, weights_int, kw, kh, anchor=None, border="zero"):
+    """([Galois element], [G][n] slot values modulo t) of a kw x kh filter over packed tiles that is right at the tile border, for
+    RotDiagPlan / Evaluator.rotate_diag_sum: tap (i, j) is the rotation by (j - ay) tile_w + (i - ax), and its diagonal holds, per slot
+    (y, x) of the tile (both rows of n/2 slots alike),
+        border="zero":   w[j][i] where the source (y + j - ay, x + i - ax) lies inside the tile, 0 elsewhere;
+        border="clamp":  clamp-to-edge -- a source outside the tile is the nearest pixel inside it, so w[j][i] is added to the diagonal of
+                         the tap that reads THAT pixel from (y, x).  With the anchor inside the kernel the clamped offset lies between 0
+                         and the tap's own, inside the kernel's own set of rotations: no further key is needed.
+    Taps whose diagonal is 0 in every slot are left out; the tap that does not move is element 1."""
+    from .keys import galois_element
+    if border not in ("zero", "clamp"):
+        raise ValueError("packed_filter_diagonals: border %r (zero, clamp)" % (border,))
+    ax, ay = filter_anchor(kw, kh) if anchor is None else anchor
+    w = [int(v) for v in np.asarray(weights_int).reshape(-1)]
+    if len(w) != kw * kh:
+        raise ValueError("packed_filter_diagonals: %d weights for a %d x %d kernel" % (len(w), kw, kh))
+    half = n // 2
+    if tile_w <= 0 or half % tile_w:
+        raise ValueError("packed_filter_diagonals: tile_w = %d does not divide the row of %d slots" % (tile_w, half))
+    if border == "clamp" and not (0 <= ax < kw and 0 <= ay < kh):
+        raise ValueError("packed_filter_diagonals: border=\"clamp\" needs the anchor inside the kernel")
+    tile_h = half // tile_w
+    y, x = np.divmod(np.arange(half), tile_w)
+    diag = {}                                                           # (dy, dx) -> [half] int64 modulo t
+    for p, wp in enumerate(w):
+        if wp % t == 0:
+            continue
+        j, i = divmod(p, kw)
+        dy, dx = j - ay, i - ax
+        sy, sx = y + dy, x + dx
+        inside = (sy >= 0) & (sy < tile_h) & (sx >= 0) & (sx < tile_w)
+        if border == "zero":
+            d = diag.setdefault((dy, dx), np.zeros(half, dtype=np.int64))
+            d[inside] = (d[inside] + wp) % t
+            continue
+        cy, cx = np.clip(sy, 0, tile_h - 1) - y, np.clip(sx, 0, tile_w - 1) - x
+        for off in set(zip(cy.tolist(), cx.tolist())):
+            sel = (cy == off[0]) & (cx == off[1])
+            d = diag.setdefault(off, np.zeros(half, dtype=np.int64))
+            d[sel] = (d[sel] + wp) % t
+    elts, rows = [], []
+    for (dy, dx), d in sorted(diag.items()):
+        if not d.any():
+            continue
+        elts.append(galois_element(n, dy * tile_w + dx))
+        rows.append(np.concatenate([d, d]).astype(np.uint64))
+    if not elts:
+        raise ValueError("packed_filter_diagonals: every weight is zero modulo t")
+    if len(set(elts)) != len(elts):
+        raise ValueError("packed_filter_diagonals: two taps of this kernel are the same rotation of the tile")
+    return elts, np.stack(rows)
+
+
+def packed_filter_border_model(tile, weights_int, kw, kh, t, anchor=None, border="zero"):
+    """plain numpy: the bordered filter of one tile [tile_h][tile_w] of integers, modulo t (what every slot of
+    packed_filter2d(border=...) decrypts to)"""
+    ax, ay = filter_anchor(kw, kh) if anchor is None else anchor
+    tile = np.asarray(tile).astype(object)
+    th, tw = tile.shape
+    w = np.asarray(weights_int).reshape(kh, kw)
+    out = np.zeros((th, tw), dtype=object)
+    for yy in range(th):
+        for xx in range(tw):
+            acc = 0
+            for j in range(kh):
+                for i in range(kw):
+                    sy, sx = yy + j - ay, xx + i - ax
+                    if border == "clamp":
+                        sy, sx = min(max(sy, 0), th - 1), min(max(sx, 0), tw - 1)
+                    elif not (0 <= sy < th and 0 <= sx < tw):
+                        continue
+                    acc += int(w[j][i]) * int(tile[sy][sx])
+            out[yy][xx] = acc % t
+    return out
+
+
+def block_matvec_diagonals(n, t, B):
+    """([Galois element], [G][n] slot values modulo t) of the d x d integer matrix B applied to every aligned group of d slots of both rows
+    (the diagonal method): out[g d + a] = sum_b B[a][b] x[g d + b].  d divides n/2.  The steps are -(d - 1) .. d - 1, B[a][b] sits on the
+    diagonal of step b - a at the slots = a modulo d; a read that would leave its group meets a 0.  All-zero diagonals are left out."""
+    from .keys import galois_element
+    B = np.asarray(B)
+    if B.ndim != 2 or B.shape[0] != B.shape[1] or B.shape[0] < 1:
+        raise ValueError("block_matvec_diagonals: a square matrix expected, got shape %r" % (tuple(B.shape),))
+    d, half = int(B.shape[0]), n // 2
+    if half % d:
+        raise ValueError("block_matvec_diagonals: d = %d does not divide the row of %d slots" % (d, half))
+    a = np.arange(n) % d                                                # half is a multiple of d: the same in both rows
+    elts, rows = [], []
+    for s in range(-(d - 1), d):
+        row = np.array([int(B[ai][ai + s]) % t if 0 <= ai + s < d else 0 for ai in a], dtype=np.uint64)
+        if not row.any():
+            continue
+        elts.append(galois_element(n, s))
+        rows.append(row)
+    if not elts:
+        raise ValueError("block_matvec_diagonals: the matrix is zero modulo t")
+    return elts, np.stack(rows)
+
+
+def rotate_diag_budget(ctx, budget_bits, plains, noise_bound=None):
+    """Lower bound (bits, float) on the invariant noise budget after ONE Evaluator.rotate_diag_sum (fhe_rotate_diag_sum_sp), from the
+    budget before: rotate_sum_budget's formula with W = sum_j ||p'_j||_1, the l1 norm of the centred lift of tap j's plaintext
+    (RotDiagPlan.plains: COEFFICIENTS modulo t, not slot values).  A negacyclic product with p'_j scales the coefficients of the input's
+    invariant noise, and of the key-switch term, by at most that; the one rounding is as it was.  `ctx` is the PARENT context."""
+    from fractions import Fraction
+    q, n, t = [int(x) for x in ctx.q], int(ctx.n), int(ctx.t)
+    if len(q) < 2:
+        raise ValueError("rotate_diag_budget: a context of %d prime(s); the last of at least 2 is the special prime" % len(q))
+    P = np.asarray(plains)
+    if P.ndim != 2 or P.shape[0] < 1:
+        raise ValueError("rotate_diag_budget: plaintexts [G][n] expected")
+    W = 0
+    for row in P:
+        c = [int(v) % t for v in row]
+        if not any(c):
+            raise ValueError("rotate_diag_budget: a plaintext is the zero polynomial")
+        W += sum(t - v if 2 * v > t else v for v in c)
     if noise_bound is None:
         from .keys import _Sampler
         noise_bound = _Sampler.NOISE_MAX

@@ -459,6 +459,68 @@ class RotSumPlan:
             self.h = None
 
 
+class RotDiagPlan:
+    """The taps of Evaluator.rotate_diag_sum (fhe_rotdiag_plan_create: a diagonal linear map on the slots of ONE ciphertext under one
+    special-prime key switch): out = sum_j d_j (.) rot_j(x) slot by slot.  ctx_level, special_galois_keys, elements_or_steps and steps are
+    RotSumPlan's; diagonals: [G][n] slot values modulo t in flat row order (row 0 then row 1), none of them all zero -- they go through
+    client.BatchEncoder, and the diagonal multiplies AFTER the rotation.  The plan keeps the key tensors alive: the library holds their
+    device pointers."""
+
+    MAX_TAPS = 64
+
+    def __init__(self, ctx_level, special_galois_keys, elements_or_steps, diagonals, steps=False):
+        from .client import BatchEncoder
+        from .keys import SpecialGaloisKeys, galois_element                # keys.py imports this module
+        keys = special_galois_keys
+        if not isinstance(keys, SpecialGaloisKeys):
+            raise ValueError("RotDiagPlan: SpecialGaloisKeys expected (KeyGenerator.generate_special_galois_keys), got %s" % type(keys).__name__)
+        n, t = int(ctx_level.n), int(ctx_level.t)
+        elts = [galois_element(n, int(v)) if steps else int(v) for v in elements_or_steps]
+        if not 1 <= len(elts) <= self.MAX_TAPS:
+            raise ValueError("RotDiagPlan: %d taps (1 .. %d)" % (len(elts), self.MAX_TAPS))
+        d = np.asarray(diagonals)
+        if d.ndim != 2 or d.shape != (len(elts), n):
+            raise ValueError("RotDiagPlan: diagonals of shape %r for %d taps of %d slots" % (tuple(d.shape), len(elts), n))
+        d = np.array([[int(v) % t for v in row] for row in d], dtype=np.uint64)
+        for j, g in enumerate(elts):
+            if not (g & 1) or not 0 < g < 2 * n:
+                raise ValueError("RotDiagPlan: Galois element %d must be odd and in [1, 2n = %d)" % (g, 2 * n))
+            if g in elts[:j]:
+                raise ValueError("RotDiagPlan: Galois element %d is repeated" % g)
+            if not d[j].any():
+                raise ValueError("RotDiagPlan: the diagonal of tap %d is 0 modulo t in every slot" % j)
+        self._keys = []
+        for g in elts:
+            if g == 1:
+                self._keys.append(None)
+                continue
+            if not keys.has(g):
+                raise ValueError("RotDiagPlan: no special Galois key for element %d (have %r); the fused call takes no hops" % (g, keys.elements()))
+            key = keys.key(g)
+            check_special_keys(ctx_level, keys.ctx, key, 1, "RotDiagPlan")   # the checks apply_galois makes before a bare pointer is handed over
+            self._keys.append(key)
+        self.ctx, self.parent, self.elements = ctx_level, keys.ctx, elts
+        self.plains = np.ascontiguousarray(BatchEncoder(ctx_level).encode_host(d), dtype=np.uint64)      # [G][n] coefficients modulo t
+        e = np.array(elts, dtype=np.uint32)
+        kp = (C.c_void_p * len(elts))(*[None if k is None else k.data_ptr() for k in self._keys])
+        h = C.c_void_p()
+        torch.cuda.synchronize(ctx_level.device)                             # the keys are complete before the plan's own (null-stream) transforms
+        _lib.call("fhe_rotdiag_plan_create", keys.ctx.h, len(elts), e.ctypes.data_as(C.c_void_p), self.plains.ctypes.data_as(C.c_void_p), kp, C.byref(h))
+        self.h = h
+
+    def scratch_bytes(self, count):
+        return int(_lib.load().fhe_rotdiag_scratch_bytes(self.h, int(count)))
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h:
+            try:
+                _lib.load().fhe_rotdiag_plan_destroy(h)
+            except Exception:
+                pass
+            self.h = None
+
+
 def check_evaluation_keys(ctx, evk_ntt, dbc, need, who):
     """The library takes the keys as a bare pointer and reads need * fhe_evk_words(ctx, dbc) words behind it (include/fhe_hip.h): the host
     checks that the tensor it hands over holds them -- a key tensor made for another decomposition bit count (fewer digits), another context or
@@ -737,9 +799,10 @@ class Evaluator:
         _lib.call("fhe_apply_galois", self.ctx.h, _ptr(a), ctw, _ptr(out), ctw, count, g, _ptr(key), keys.dbc, _ptr(scr), nbytes, _stream())
         return out
 
-    def _rotsum_operand(self, a, plan, who):
-        if not isinstance(plan, RotSumPlan):
-            raise ValueError("%s: a RotSumPlan expected, got %s" % (who, type(plan).__name__))
+    def _rotsum_operand(self, a, plan, who, kind=None):
+        kind = RotSumPlan if kind is None else kind
+        if not isinstance(plan, kind):
+            raise ValueError("%s: a %s expected, got %s" % (who, kind.__name__, type(plan).__name__))
         c = plan.ctx
         if (c.n, c.k, c.t, c.device) != (self.ctx.n, self.ctx.k, self.ctx.t, self.ctx.device) or list(c.q) != list(self.ctx.q):
             raise ValueError("%s: the plan was made for another context" % who)
@@ -760,6 +823,21 @@ class Evaluator:
         nbytes = plan.scratch_bytes(count)
         scr = self._scratch_buf(nbytes)
         _lib.call("fhe_rotate_sum_sp", plan.h, _ptr(a), ctw, _ptr(out), ctw, count, _ptr(scr), nbytes, _stream())
+        return out
+
+    def rotate_diag_sum(self, a, plan, out=None):
+        """sum over the plan's taps of d_j (.) rot_j(a) slot by slot, key-switched back to s ONCE (fhe_rotate_diag_sum_sp): rotate_sum with
+        a vector of slot values per tap where it has one integer -- the diagonal method for a matrix applied to the slot vector, a filter
+        that is right at the tile border, a masked move of slots.  Decrypts to what the composition of apply_galois, multiply_plain by the
+        encoded diagonal and add decrypts to; the ciphertext bits are its own.  `out` as for rotate_sum."""
+        count = self._rotsum_operand(a, plan, "rotate_diag_sum", RotDiagPlan)
+        if out is not None and (tuple(out.shape) != tuple(a.shape) or out.dtype != a.dtype or not out.is_contiguous() or out.device != a.device):
+            raise ValueError("rotate_diag_sum: `out` must be a contiguous int64 tensor of shape %r on the input's device" % (tuple(a.shape),))
+        out = torch.empty_like(a) if out is None else out
+        ctw = 2 * self.ctx.k * self.ctx.n
+        nbytes = plan.scratch_bytes(count)
+        scr = self._scratch_buf(nbytes)
+        _lib.call("fhe_rotate_diag_sum_sp", plan.h, _ptr(a), ctw, _ptr(out), ctw, count, _ptr(scr), nbytes, _stream())
         return out
 
     def rotate_each(self, a, plan):

@@ -20,6 +20,8 @@
 //   relinearize_sp, apply_galois_sp, rotate_rows_sp, rotate_columns_sp
 //   seal::hip::RotSumPlan,       hoisted special-prime rotations of one ciphertext (fhe_rotate_sum_sp / fhe_rotate_each_sp): a weighted sum of
 //   rotate_sum_sp, rotate_each_sp  rotations with ONE key-switch tail, or the rotations as separate batches with the forward transforms shared
+//   seal::hip::RotDiagPlan,      diagonal linear maps on the slots of one ciphertext (fhe_rotate_diag_sum_sp): per-slot weights inside the fused
+//   rotate_diag_sum_sp             sum -- filters that are right at the tile border, small matrices on groups of slots, masked moves
 //
 // (The slot encoder and the Galois rotations -- seal::hip::batch_encode / batch_decode, GaloisKeys, generate_galois_keys, apply_galois,
 // rotate_rows, rotate_columns -- work on std::vector<seal::Ciphertext> and live in seal/seal.h, beside filter2d and remap.)
@@ -640,6 +642,43 @@ inline CiphertextBatch rotate_each_sp(const SEALContext &parent, const SEALConte
                                      nullptr), "rotate_each_sp");
     detail::check(fhe_stream_sync(nullptr), "sync");
     return out;
+}
+
+// ---- diagonal linear maps on encrypted slots (include/fhe_hip.h: fhe_rotdiag_plan_create, fhe_rotate_diag_sum_sp) -----------------------------
+// RotSumPlan with a vector of n slot values (flat row order, below t, not all zero) per tap where it has one integer: the plan batch-encodes
+// them (fhe_batch_encode) and the diagonal multiplies AFTER the rotation, out = sum_j d_j (.) rot_j(x) slot by slot.  `keys` must outlive it.
+class RotDiagPlan {
+public:
+    RotDiagPlan(const SEALContext &parent, const SpecialGaloisKeys &keys, const std::vector<uint32_t> &elements, const std::vector<uint64_t> &diagonals)
+        : h_(nullptr), taps_(elements.size()) {
+        const uint32_t n = parent.state()->n;
+        if (diagonals.size() != elements.size() * (size_t)n) throw std::invalid_argument("RotDiagPlan: n slot values per tap");
+        std::vector<uint64_t> plains(diagonals.size());
+        if (!elements.empty()) detail::check(fhe_batch_encode(n, parent.state()->t, diagonals.data(), elements.size(), plains.data()), "RotDiagPlan");
+        std::vector<const uint64_t *> ptrs(elements.size(), nullptr);
+        for (size_t j = 0; j < elements.size(); ++j)
+            if (elements[j] != 1) ptrs[j] = keys.key(parent, elements[j]);
+        detail::check(fhe_stream_sync(nullptr), "sync");                     // the keys' uploads are complete
+        detail::check(fhe_rotdiag_plan_create(parent.state()->h, (uint32_t)elements.size(), elements.data(), plains.data(), ptrs.data(), &h_), "RotDiagPlan");
+    }
+    ~RotDiagPlan() { fhe_rotdiag_plan_destroy(h_); }
+    RotDiagPlan(const RotDiagPlan &) = delete;
+    RotDiagPlan &operator=(const RotDiagPlan &) = delete;
+    const fhe_rotdiag_plan *handle() const { return h_; }
+    size_t taps() const { return taps_; }
+private:
+    fhe_rotdiag_plan *h_;
+    size_t taps_;
+};
+// Evaluator.rotate_diag_sum of the Python host, in place on a batch of size-2 ciphertexts of `level`
+inline void rotate_diag_sum_sp(const SEALContext &parent, const SEALContext &level, CiphertextBatch &cts, const RotDiagPlan &plan) {
+    check_special_level(parent, level, cts, "rotate_diag_sum_sp");
+    if (cts.count() && cts.size() != 2) throw std::invalid_argument("rotate_diag_sum_sp needs size-2 ciphertexts (relinearize first)");
+    if (!cts.count()) return;
+    const size_t bytes = fhe_rotdiag_scratch_bytes(plan.handle(), cts.count());
+    detail::DevBuf scratch((bytes + 7) / 8 + 1);
+    detail::check(fhe_rotate_diag_sum_sp(plan.handle(), cts.ptr(), cts.ct_words(), cts.ptr(), cts.ct_words(), cts.count(), scratch.ptr(), bytes, nullptr), "rotate_diag_sum_sp");
+    detail::check(fhe_stream_sync(nullptr), "sync");
 }
 
 }  // namespace hip

@@ -87,7 +87,8 @@ const char *fhe_last_error(void);
  *      fhe_ctx_create_level and fhe_mod_switch (modulus switching: dropping RNS primes from ciphertexts), and for fhe_ksk_sp_words,
  *      fhe_key_switch_sp_scratch_bytes, fhe_relinearize_sp_poly and fhe_apply_galois_sp (key switching with a special prime), and for
  *      fhe_rotsum_plan_create / destroy, fhe_rotsum_scratch_bytes, fhe_rotate_sum_sp and fhe_rotate_each_sp (hoisted special-prime
- *      rotations of one ciphertext and their fused weighted sum).
+ *      rotations of one ciphertext and their fused weighted sum), and for fhe_rotdiag_plan_create / destroy, fhe_rotdiag_scratch_bytes and
+ *      fhe_rotate_diag_sum_sp (diagonal linear maps on encrypted slots: per-slot plaintext weights inside the fused sum).
  * A host compiled against this header compares fhe_abi_version() with FHE_ABI_VERSION before anything else (the Python
  * binding and seal/seal.h do). */
 #define FHE_ABI_VERSION 4
@@ -499,6 +500,35 @@ int fhe_rotate_sum_sp(const fhe_rotsum_plan *plan, const uint64_t *ct2, uint64_t
                       uint64_t count, void *scratch, size_t scratch_bytes, fhe_stream stream);
 int fhe_rotate_each_sp(const fhe_rotsum_plan *plan, const uint64_t *ct2, uint64_t ct_stride_words, uint64_t *out, uint64_t out_stride_words,
                        uint64_t tap_stride_words, uint64_t count, void *scratch, size_t scratch_bytes, fhe_stream stream);
+
+/* ---- diagonal linear maps on the slots of ONE ciphertext under one special-prime key switch (csrc/rotdiag.hip) ------------------------------
+ * fhe_rotate_sum_sp with a plaintext POLYNOMIAL per tap where it has one integer: out = sum_j p_j * rot_(g_j)(ct), the diagonal method's
+ * sum_j d_j (.) rot_j(x) on the slots when p_j is the batch encoding of d_j.  Setting, level, key layout [L][2][k][n] and drop are those above.
+ * A plan holds G taps, 1 <= G <= 64: pairwise distinct Galois elements g_j, odd, in [1, 2n) (g = 1: no rotation, no key), plaintexts p_j of n
+ * coefficients modulo t, not the zero polynomial, with p'_j the centred lift (coefficients in (-t/2, t/2], reduced to every q_r: the lift of
+ * fhe_multiply_plain), and K_j, the special Galois key for sigma_(g_j)(s) (may be null for g = 1).  With D_i,r and pi_g as above and
+ * P_j,r = NTT_(q_r)(p'_j) in the context's own slot order:
+ *   acc_pp,r = sum_(j: g_j != 1) P_j,r (*) sum_(i < L) pi_(g_j)(D_i,r) (*) K_j,i,pp,r  mod q_r   for every r < k,
+ *   u_pp     = one drop (k -> k - 1) of acc_pp, bit for bit fhe_mod_switch's,
+ *   out_0    = u_0 + sum_j p'_j sigma_(g_j)(c_0),    out_1 = u_1 + sum_(j: g_j = 1) p'_j c_1      (products in R_(q_r)).
+ * All results are fully reduced.  The diagonal multiplies AFTER the rotation: tap j is multiply_plain(rotate(ct, g_j), p_j), and the result
+ * decrypts to what that op-by-op composition decrypts to; its ciphertext bits are its own (the digit reason above).  When every p_j is a
+ * constant polynomial w_j the definition is fhe_rotate_sum_sp's with the weights w_j: the same bytes.
+ * Noise: fhe_rotate_sum_sp's bound with W = sum_j ||p'_j||_1 (circuits.rotate_diag_budget in the Python host).
+ * plains_host [G][n] is HOST memory, read during plan creation only.  The plan keeps on the device the permutation tables, the key POINTER
+ * table (the keys must stay where they are while the plan is used) and P [G][k][n], taken through the context's own forward transform, so
+ * its slot order is that of D and of the keys on every path.  Plan creation allocates, launches and synchronises; the call does none of these.
+ * In place: out2 == ct2 with equal strides is allowed; every other overlap is refused.
+ * Refused (FHE_ERR_PARAM) before anything is enqueued: everything fhe_rotsum_plan_create / fhe_rotate_sum_sp refuse (the weight's check
+ * becomes the plaintext's), a plaintext coefficient >= t, an all-zero plaintext, scratch_bytes < fhe_rotdiag_scratch_bytes(plan, count).
+ * count == 0 is a no-op. */
+typedef struct fhe_rotdiag_plan fhe_rotdiag_plan;
+int fhe_rotdiag_plan_create(const fhe_ctx *ctx, uint32_t taps, const uint32_t *galois_elts, const uint64_t *plains_host,
+                            const uint64_t *const *d_keys_ntt, fhe_rotdiag_plan **out);
+int fhe_rotdiag_plan_destroy(fhe_rotdiag_plan *plan);
+size_t fhe_rotdiag_scratch_bytes(const fhe_rotdiag_plan *plan, uint64_t count);
+int fhe_rotate_diag_sum_sp(const fhe_rotdiag_plan *plan, const uint64_t *ct2, uint64_t ct_stride_words, uint64_t *out2, uint64_t out_stride_words,
+                           uint64_t count, void *scratch, size_t scratch_bytes, fhe_stream stream);
 
 /* ---- fused block circuit: encrypted_dct (homo/fhe_image.h:196-288) followed by quantize_fhe
  * (homo/fhe_image.h:294-305) on n_blocks independent 8x8 blocks.  in/out: [n_blocks][64][2][k][n].
