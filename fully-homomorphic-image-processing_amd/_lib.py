@@ -111,6 +111,10 @@ SIGNATURES = {
     "fhe_rotdiag_plan_destroy": (_i, [_vp]),
     "fhe_rotdiag_scratch_bytes": (_sz, [_vp, _u64]),
     "fhe_rotate_diag_sum_sp": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _sz, _vp]),
+    "fhe_rotbsgs_plan_create": (_i, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "fhe_rotbsgs_plan_destroy": (_i, [_vp]),
+    "fhe_rotbsgs_scratch_bytes": (_sz, [_vp, _u64]),
+    "fhe_rotate_bsgs_sp": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _sz, _vp]),
     "fhe_dct_plan_create": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(_vp)]),
     "fhe_dct_plan_destroy": (_i, [_vp]),
     "fhe_dct8x8_scratch_bytes": (_sz, [_vp, _u64]),

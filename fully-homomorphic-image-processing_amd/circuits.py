@@ -1118,6 +1118,90 @@ def rotate_diag_budget(ctx, budget_bits, plains, noise_bound=None):
     return math.log2(total.denominator) - math.log2(total.numerator)
 
 
+def bsgs_split(n, steps, diagonals, baby=None):
+    """(baby steps, giant steps, [G2][G1][n] slot values) for RotBsgsPlan(steps=True) from the diagonal form out = sum_s d_s (.) rot_s(x)
+    (element 3^s rotates both rows of n/2 slots LEFT by s; steps are signed integers, pairwise distinct as rotations).  Step s is split as
+    s = baby a + j with 0 <= j < baby and a = floor(s / baby): baby step j, giant step baby a.  Since rot_g(d (.) y) = rot_g(d) (.) rot_g(y),
+    diagonal s is pre-rotated by -baby a within each row: d'_(a,j) = rot_(-baby a)(d_s).  Pairs without a diagonal are all zero (absent).
+    baby=None: the power of two nearest sqrt(number of steps)."""
+    steps = [int(s) for s in steps]
+    d = np.asarray(diagonals)
+    half = n // 2
+    if d.ndim != 2 or d.shape != (len(steps), n) or not steps:
+        raise ValueError("bsgs_split: diagonals of shape %r for %d steps of %d slots" % (tuple(d.shape), len(steps), n))
+    if len(set(s % half for s in steps)) != len(steps):
+        raise ValueError("bsgs_split: two steps are the same rotation of a row of %d slots" % half)
+    if baby is None:
+        baby = 1 << max(0, int(round(math.log2(math.sqrt(len(steps))))))
+    baby = int(baby)
+    if baby < 1:
+        raise ValueError("bsgs_split: baby = %d" % baby)
+    split = [(s // baby, s % baby) for s in steps]                      # Python's floor division: a < 0 for s < 0, j in [0, baby)
+    bs = sorted(set(j for _, j in split))
+    gs = sorted(set(a for a, _ in split))
+    out = np.zeros((len(gs), len(bs), n), dtype=d.dtype)
+    for (a, j), row in zip(split, d):
+        out[gs.index(a), bs.index(j)] = np.roll(np.asarray(row).reshape(2, half), baby * a, axis=1).reshape(n)
+    return bs, [baby * a for a in gs], out
+
+
+def block_matvec_bsgs(n, t, B, baby=None):
+    """bsgs_split of block_matvec_diagonals(n, t, B): (baby steps, giant steps, [G2][G1][n]) of the d x d matrix B on every aligned group of
+    d slots, 2 d - 1 diagonals under about 2 sqrt(2 d) keys"""
+    from .keys import galois_element
+    elts, diags = block_matvec_diagonals(n, t, B)
+    d = int(np.asarray(B).shape[0])
+    step_of = {galois_element(n, s): s for s in range(-(d - 1), d)}
+    return bsgs_split(n, [step_of[g] for g in elts], diags, baby)
+
+
+def block_dct2d_matrix(bits=8):
+    """[64][64] int64: D (x) D for D = dct8_matrix(bits) -- the 2-D 8 x 8 DCT of a block held row-major in 64 consecutive slots:
+    out[8 u + v] = sum_(y, x) D[u][y] D[v][x] block[8 y + x], scaled by 2^(2 bits)"""
+    D = dct8_matrix(bits)
+    return np.kron(D, D).astype(np.int64)
+
+
+def rotate_bsgs_budget(ctx, budget_bits, plains, baby, giant, noise_bound=None):
+    """Lower bound (bits, float) on the invariant noise budget after ONE Evaluator.rotate_bsgs (fhe_rotate_bsgs_sp), from the budget before.
+    `ctx` is the PARENT context; plains [G2][G1][n] are RotBsgsPlan.plains (COEFFICIENTS modulo t, all zero = absent); baby / giant the
+    Galois elements (only "is it 1" matters).  With W_i = sum_j ||p'_(i,j)||_1, S = sum_(l < L) (q_l - 1) and B the key noise bound, the
+    phase of the result is
+        sum_i sigma_(h_i)(X_i)  +  sum_i [ sigma_(h_i)(N_i) / p  +  [h_i != 1] (sigma_(h_i)(rho_i s) + N'_i / p) ]  +  rho_0 + rho_1 s     (mod Q)
+      * X_i = sum_j p'_(i,j) sigma_(g_j)(c_0 + c_1 s): the input's invariant noise scaled by at most sum_i W_i;
+      * N_i, the inner key-switch terms under the plaintext products: at most W_i n B S each;
+      * rho_i, the rounding of v(i), times the ternary secret: n / 2 per non-identity giant step;
+      * N'_i, one key switch of v(i) (digits below q_l): n B S per non-identity giant step;
+      * the final rounding: (1 + n) / 2.
+        E = (sum_i W_i + G') n B S / p + G' n / 2 + (1 + n) / 2,   G' = #{i: h_i != 1},      B_after >= -log2(sum_i W_i 2^-B_before + 2 t E / Q).
+    With G2 = 1 and h = {1} this is rotate_diag_budget."""
+    from fractions import Fraction
+    q, n, t = [int(x) for x in ctx.q], int(ctx.n), int(ctx.t)
+    if len(q) < 2:
+        raise ValueError("rotate_bsgs_budget: a context of %d prime(s); the last of at least 2 is the special prime" % len(q))
+    P = np.asarray(plains)
+    giant = [int(h) for h in giant]
+    if P.ndim != 3 or P.shape[0] != len(giant) or P.shape[1] != len(list(baby)) or P.shape[0] < 1 or P.shape[1] < 1:
+        raise ValueError("rotate_bsgs_budget: plaintexts [G2][G1][n] expected, one row per giant and one column per baby step")
+    W = 0
+    for row in P:
+        Wi = 0
+        for pl in row:
+            Wi += sum(t - v if 2 * v > t else v for v in (int(x) % t for x in pl))
+        if not Wi:
+            raise ValueError("rotate_bsgs_budget: a giant step has no present pair")
+        W += Wi
+    Gn = sum(h != 1 for h in giant)
+    if noise_bound is None:
+        from .keys import _Sampler
+        noise_bound = _Sampler.NOISE_MAX
+    p, Q = q[-1], math.prod(q[:-1])
+    E = Fraction((W + Gn) * n * int(noise_bound) * sum(qi - 1 for qi in q[:-1]), p) + Fraction(Gn * n, 2) + Fraction(1 + n, 2)
+    before = Fraction(1, 1 << int(budget_bits)) if float(budget_bits) == int(budget_bits) else Fraction(2.0 ** -float(budget_bits))
+    total = W * before + 2 * t * E / Q
+    return math.log2(total.denominator) - math.log2(total.numerator)
+
+
 def mod_switch_primes(ctx, budget_bits, keep_bits, size=2):
     """The smallest k_out whose mod_switch_budget is at least keep_bits; ctx.k (no switch) when not even one drop qualifies."""
     k = len(ctx.q)

@@ -521,6 +521,89 @@ class RotDiagPlan:
             self.h = None
 
 
+class RotBsgsPlan:
+    """The plan of Evaluator.rotate_bsgs (fhe_rotbsgs_plan_create: a baby-step / giant-step linear map on the slots of ONE ciphertext):
+    out = sum_i rot_(h_i)( sum_j d_(i,j) (.) rot_(g_j)(x) ) slot by slot, G1 G2 diagonals under G1 + G2 keys.  ctx_level,
+    special_galois_keys and steps are RotSumPlan's; baby / giant: the two lists of Galois elements (or row rotations LEFT with steps=True),
+    each odd, pairwise distinct, 1 = no rotation, no key; diagonals: [G2][G1][n] slot values modulo t in flat row order -- they go through
+    client.BatchEncoder; a diagonal that is 0 in every slot means the pair is absent.  circuits.bsgs_split makes the three from the
+    diagonals of a map.  The plan keeps the key tensors alive: the library holds their device pointers."""
+
+    MAX_STEPS = 64
+
+    def __init__(self, ctx_level, special_galois_keys, baby, giant, diagonals, steps=False):
+        from .client import BatchEncoder
+        from .keys import SpecialGaloisKeys, galois_element                # keys.py imports this module
+        keys = special_galois_keys
+        if not isinstance(keys, SpecialGaloisKeys):
+            raise ValueError("RotBsgsPlan: SpecialGaloisKeys expected (KeyGenerator.generate_special_galois_keys), got %s" % type(keys).__name__)
+        n, t = int(ctx_level.n), int(ctx_level.t)
+        lists = []
+        for what, vals in (("baby", baby), ("giant", giant)):
+            elts = [galois_element(n, int(v)) if steps else int(v) for v in vals]
+            if not 1 <= len(elts) <= self.MAX_STEPS:
+                raise ValueError("RotBsgsPlan: %d %s steps (1 .. %d)" % (len(elts), what, self.MAX_STEPS))
+            for j, g in enumerate(elts):
+                if not (g & 1) or not 0 < g < 2 * n:
+                    raise ValueError("RotBsgsPlan: %s Galois element %d must be odd and in [1, 2n = %d)" % (what, g, 2 * n))
+                if g in elts[:j]:
+                    raise ValueError("RotBsgsPlan: %s Galois element %d is repeated" % (what, g))
+            lists.append(elts)
+        b, g = lists
+        d = np.asarray(diagonals)
+        if d.ndim != 3 or d.shape != (len(g), len(b), n):
+            raise ValueError("RotBsgsPlan: diagonals of shape %r for %d giant and %d baby steps of %d slots" % (tuple(d.shape), len(g), len(b), n))
+        if d.dtype == object:                                                # Python integers of any size
+            d = np.array([int(v) % t for v in d.reshape(-1)], dtype=np.uint64).reshape(d.shape)
+        elif d.dtype.kind in "iu":
+            d = (d % np.uint64(t) if d.dtype == np.uint64 else d.astype(np.int64) % np.int64(t)).astype(np.uint64)
+        else:
+            raise ValueError("RotBsgsPlan: integer diagonals expected, got dtype %s" % d.dtype)
+        present = d.any(axis=2)
+        for i in range(len(g)):
+            if not present[i].any():
+                raise ValueError("RotBsgsPlan: giant step %d has no present pair (every diagonal of its row is 0 modulo t)" % i)
+        for j in range(len(b)):
+            if not present[:, j].any():
+                raise ValueError("RotBsgsPlan: baby step %d has no present pair (every diagonal of its column is 0 modulo t)" % j)
+        self._keys = []
+        for elts in lists:
+            row = []
+            for e in elts:
+                if e == 1:
+                    row.append(None)
+                    continue
+                if not keys.has(e):
+                    raise ValueError("RotBsgsPlan: no special Galois key for element %d (have %r); the fused call takes no hops" % (e, keys.elements()))
+                key = keys.key(e)
+                check_special_keys(ctx_level, keys.ctx, key, 1, "RotBsgsPlan")   # the checks apply_galois makes before a bare pointer is handed over
+                row.append(key)
+            self._keys.append(row)
+        self.ctx, self.parent, self.baby, self.giant = ctx_level, keys.ctx, b, g
+        enc = BatchEncoder(ctx_level).encode_host(d.reshape(len(g) * len(b), n))
+        self.plains = np.ascontiguousarray(np.asarray(enc, dtype=np.uint64).reshape(len(g), len(b), n))      # [G2][G1][n] coefficients modulo t
+        eb, eg = np.array(b, dtype=np.uint32), np.array(g, dtype=np.uint32)
+        kb = (C.c_void_p * len(b))(*[None if k is None else k.data_ptr() for k in self._keys[0]])
+        kg = (C.c_void_p * len(g))(*[None if k is None else k.data_ptr() for k in self._keys[1]])
+        h = C.c_void_p()
+        torch.cuda.synchronize(ctx_level.device)                             # the keys are complete before the plan's own (null-stream) transforms
+        _lib.call("fhe_rotbsgs_plan_create", keys.ctx.h, len(b), eb.ctypes.data_as(C.c_void_p), len(g), eg.ctypes.data_as(C.c_void_p),
+                  self.plains.ctypes.data_as(C.c_void_p), kb, kg, C.byref(h))
+        self.h = h
+
+    def scratch_bytes(self, count):
+        return int(_lib.load().fhe_rotbsgs_scratch_bytes(self.h, int(count)))
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h:
+            try:
+                _lib.load().fhe_rotbsgs_plan_destroy(h)
+            except Exception:
+                pass
+            self.h = None
+
+
 def check_evaluation_keys(ctx, evk_ntt, dbc, need, who):
     """The library takes the keys as a bare pointer and reads need * fhe_evk_words(ctx, dbc) words behind it (include/fhe_hip.h): the host
     checks that the tensor it hands over holds them -- a key tensor made for another decomposition bit count (fewer digits), another context or
@@ -838,6 +921,20 @@ class Evaluator:
         nbytes = plan.scratch_bytes(count)
         scr = self._scratch_buf(nbytes)
         _lib.call("fhe_rotate_diag_sum_sp", plan.h, _ptr(a), ctw, _ptr(out), ctw, count, _ptr(scr), nbytes, _stream())
+        return out
+
+    def rotate_bsgs(self, a, plan, out=None):
+        """sum_i rot_(h_i)( sum_j d_(i,j) (.) rot_(g_j)(a) ) slot by slot (fhe_rotate_bsgs_sp): the baby-step / giant-step form of
+        rotate_diag_sum, G1 + G2 keys for G1 G2 diagonals; c_0 is rounded once.  Decrypts to what the composition of rotate_each,
+        multiply_plain, add and apply_galois decrypts to; the ciphertext bits are its own.  `out` as for rotate_sum."""
+        count = self._rotsum_operand(a, plan, "rotate_bsgs", RotBsgsPlan)
+        if out is not None and (tuple(out.shape) != tuple(a.shape) or out.dtype != a.dtype or not out.is_contiguous() or out.device != a.device):
+            raise ValueError("rotate_bsgs: `out` must be a contiguous int64 tensor of shape %r on the input's device" % (tuple(a.shape),))
+        out = torch.empty_like(a) if out is None else out
+        ctw = 2 * self.ctx.k * self.ctx.n
+        nbytes = plan.scratch_bytes(count)
+        scr = self._scratch_buf(nbytes)
+        _lib.call("fhe_rotate_bsgs_sp", plan.h, _ptr(a), ctw, _ptr(out), ctw, count, _ptr(scr), nbytes, _stream())
         return out
 
     def rotate_each(self, a, plan):

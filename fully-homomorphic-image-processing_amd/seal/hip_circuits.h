@@ -22,6 +22,8 @@
 //   rotate_sum_sp, rotate_each_sp  rotations with ONE key-switch tail, or the rotations as separate batches with the forward transforms shared
 //   seal::hip::RotDiagPlan,      diagonal linear maps on the slots of one ciphertext (fhe_rotate_diag_sum_sp): per-slot weights inside the fused
 //   rotate_diag_sum_sp             sum -- filters that are right at the tile border, small matrices on groups of slots, masked moves
+//   seal::hip::RotBsgsPlan,      baby-step / giant-step linear maps on the slots of one ciphertext (fhe_rotate_bsgs_sp): G1 + G2 keys for G1 G2
+//   rotate_bsgs_sp                 diagonals -- matrices with more than 64 diagonals, the 2-D 8x8 DCT on blocks of 64 slots
 //
 // (The slot encoder and the Galois rotations -- seal::hip::batch_encode / batch_decode, GaloisKeys, generate_galois_keys, apply_galois,
 // rotate_rows, rotate_columns -- work on std::vector<seal::Ciphertext> and live in seal/seal.h, beside filter2d and remap.)
@@ -678,6 +680,50 @@ inline void rotate_diag_sum_sp(const SEALContext &parent, const SEALContext &lev
     const size_t bytes = fhe_rotdiag_scratch_bytes(plan.handle(), cts.count());
     detail::DevBuf scratch((bytes + 7) / 8 + 1);
     detail::check(fhe_rotate_diag_sum_sp(plan.handle(), cts.ptr(), cts.ct_words(), cts.ptr(), cts.ct_words(), cts.count(), scratch.ptr(), bytes, nullptr), "rotate_diag_sum_sp");
+    detail::check(fhe_stream_sync(nullptr), "sync");
+}
+
+// ---- baby-step / giant-step linear maps on encrypted slots (include/fhe_hip.h: fhe_rotbsgs_plan_create, fhe_rotate_bsgs_sp) -------------------
+// out = sum_i rot_(h_i)( sum_j d_(i,j) (.) rot_(g_j)(x) ) slot by slot: `baby` holds the G1 elements g_j, `giant` the G2 elements h_i (1 = no
+// rotation, no key), `diagonals` [G2][G1][n] slot values (flat row order, below t; all zero = the pair is absent).  The plan batch-encodes
+// them (fhe_batch_encode).  `keys` must hold every element but 1 of both lists and must outlive the plan.
+class RotBsgsPlan {
+public:
+    RotBsgsPlan(const SEALContext &parent, const SpecialGaloisKeys &keys, const std::vector<uint32_t> &baby, const std::vector<uint32_t> &giant,
+                const std::vector<uint64_t> &diagonals)
+        : h_(nullptr), baby_(baby.size()), giant_(giant.size()) {
+        const uint32_t n = parent.state()->n;
+        const size_t pairs = baby.size() * giant.size();
+        if (diagonals.size() != pairs * (size_t)n) throw std::invalid_argument("RotBsgsPlan: n slot values per (giant, baby) pair");
+        std::vector<uint64_t> plains(diagonals.size());
+        if (pairs) detail::check(fhe_batch_encode(n, parent.state()->t, diagonals.data(), pairs, plains.data()), "RotBsgsPlan");
+        std::vector<const uint64_t *> kb(baby.size(), nullptr), kg(giant.size(), nullptr);
+        for (size_t j = 0; j < baby.size(); ++j)
+            if (baby[j] != 1) kb[j] = keys.key(parent, baby[j]);
+        for (size_t i = 0; i < giant.size(); ++i)
+            if (giant[i] != 1) kg[i] = keys.key(parent, giant[i]);
+        detail::check(fhe_stream_sync(nullptr), "sync");                     // the keys' uploads are complete
+        detail::check(fhe_rotbsgs_plan_create(parent.state()->h, (uint32_t)baby.size(), baby.data(), (uint32_t)giant.size(), giant.data(), plains.data(), kb.data(),
+                                              kg.data(), &h_), "RotBsgsPlan");
+    }
+    ~RotBsgsPlan() { fhe_rotbsgs_plan_destroy(h_); }
+    RotBsgsPlan(const RotBsgsPlan &) = delete;
+    RotBsgsPlan &operator=(const RotBsgsPlan &) = delete;
+    const fhe_rotbsgs_plan *handle() const { return h_; }
+    size_t baby_steps() const { return baby_; }
+    size_t giant_steps() const { return giant_; }
+private:
+    fhe_rotbsgs_plan *h_;
+    size_t baby_, giant_;
+};
+// Evaluator.rotate_bsgs of the Python host, in place on a batch of size-2 ciphertexts of `level`
+inline void rotate_bsgs_sp(const SEALContext &parent, const SEALContext &level, CiphertextBatch &cts, const RotBsgsPlan &plan) {
+    check_special_level(parent, level, cts, "rotate_bsgs_sp");
+    if (cts.count() && cts.size() != 2) throw std::invalid_argument("rotate_bsgs_sp needs size-2 ciphertexts (relinearize first)");
+    if (!cts.count()) return;
+    const size_t bytes = fhe_rotbsgs_scratch_bytes(plan.handle(), cts.count());
+    detail::DevBuf scratch((bytes + 7) / 8 + 1);
+    detail::check(fhe_rotate_bsgs_sp(plan.handle(), cts.ptr(), cts.ct_words(), cts.ptr(), cts.ct_words(), cts.count(), scratch.ptr(), bytes, nullptr), "rotate_bsgs_sp");
     detail::check(fhe_stream_sync(nullptr), "sync");
 }
 

@@ -88,7 +88,9 @@ const char *fhe_last_error(void);
  *      fhe_key_switch_sp_scratch_bytes, fhe_relinearize_sp_poly and fhe_apply_galois_sp (key switching with a special prime), and for
  *      fhe_rotsum_plan_create / destroy, fhe_rotsum_scratch_bytes, fhe_rotate_sum_sp and fhe_rotate_each_sp (hoisted special-prime
  *      rotations of one ciphertext and their fused weighted sum), and for fhe_rotdiag_plan_create / destroy, fhe_rotdiag_scratch_bytes and
- *      fhe_rotate_diag_sum_sp (diagonal linear maps on encrypted slots: per-slot plaintext weights inside the fused sum).
+ *      fhe_rotate_diag_sum_sp (diagonal linear maps on encrypted slots: per-slot plaintext weights inside the fused sum), and for
+ *      fhe_rotbsgs_plan_create / destroy, fhe_rotbsgs_scratch_bytes and fhe_rotate_bsgs_sp (baby-step / giant-step linear maps on encrypted
+ *      slots: G1 + G2 keys for G1 G2 diagonals).
  * A host compiled against this header compares fhe_abi_version() with FHE_ABI_VERSION before anything else (the Python
  * binding and seal/seal.h do). */
 #define FHE_ABI_VERSION 4
@@ -529,6 +531,48 @@ int fhe_rotdiag_plan_destroy(fhe_rotdiag_plan *plan);
 size_t fhe_rotdiag_scratch_bytes(const fhe_rotdiag_plan *plan, uint64_t count);
 int fhe_rotate_diag_sum_sp(const fhe_rotdiag_plan *plan, const uint64_t *ct2, uint64_t ct_stride_words, uint64_t *out2, uint64_t out_stride_words,
                            uint64_t count, void *scratch, size_t scratch_bytes, fhe_stream stream);
+
+/* ---- baby-step / giant-step linear maps on the slots of ONE ciphertext (csrc/rotbsgs.hip) --------------------------------------------------
+ * out = sum_i rot_(h_i)( sum_j p_(i,j) * rot_(g_j)(ct) ): G1 G2 diagonals under G1 + G2 keys, where fhe_rotate_diag_sum_sp stops at 64 diagonals
+ * and needs a key for each.  Setting, level, key layout [L][2][k][n], pi_g, the digit convention and the drop are those above.  A plan holds
+ * G1 baby elements g_j and G2 giant elements h_i, 1 <= G1, G2 <= 64, each list odd, pairwise distinct and in [1, 2n) (1 is allowed in both
+ * and needs no key), plaintexts p_(i,j) of n coefficients modulo t (plains_host [G2][G1][n]; an all-zero plaintext = the pair is ABSENT and
+ * is skipped), and one special Galois key per non-identity baby element and per non-identity giant element.  With
+ * P_(i,j),r = NTT_(q_r)(centred lift of p_(i,j)), D_l,r = NTT_(q_r)([c_1,l]_(q_r)), C0_r = NTT_(q_r)(c_0,r) and p the special prime:
+ *   A(i)_pp,r = sum_(j present) P_(i,j),r (*) [ sum_(l < L) pi_(g_j)(D_l,r) (*) K_(g_j),l,pp,r                      (g_j != 1)
+ *                                               + [pp = 0, r < L] [p]_(q_r) pi_(g_j)(C0_r) + [pp = 1, g_j = 1, r < L] [p]_(q_r) D_r,r ]  mod q_r
+ *   v(i)      = one drop (k -> k - 1) of A(i)_1 for every i with h_i != 1, bit for bit fhe_mod_switch's, canonical coefficients,
+ *   E(i)_l,r  = NTT_(q_r)([v(i)_l]_(q_r))   (the hoisted digit: the integer in [0, q_l) reduced to q_r, pi applied in NTT form),
+ *   B_pp,r    = sum_(i: h_i != 1) [ sum_(l < L) pi_(h_i)(E(i)_l,r) (*) K_(h_i),l,pp,r + [pp = 0] pi_(h_i)(A(i)_0,r) ] + sum_(i: h_i = 1) A(i)_pp,r
+ *               for every r < k (A(i)_0 is never dropped on its own: it is permuted and added at all k primes),
+ *   out_pp    = one drop of B_pp, fully reduced.
+ * With G2 = 1 and h = {1} the result is fhe_rotate_diag_sum_sp's bytes on the taps (g_j, p_(0,j)); with G1 = 1, g = {1}, p = the constant 1 and
+ * one giant h != 1 it is fhe_rotate_sum_sp's bytes for the tap set {h} with weight 1.
+ * Noise: circuits.rotate_bsgs_budget in the Python host: c_0 is rounded once, c_1 once per non-identity giant and once more.
+ * plains_host is HOST memory, read during plan creation only.  The plan keeps on the device the permutation tables of both lists, the key
+ * POINTER tables (the keys must stay where they are while the plan is used) and P for the present pairs only, taken through the context's
+ * own forward transform.  Plan creation allocates, launches and synchronises; the call does none of these.
+ * Scratch: fhe_rotbsgs_scratch_bytes(plan, count) = 8 count n ((L k + 3 k + 2) + G2 (2 k + 1 + L + L k)) bytes: fhe_rotdiag_scratch_bytes' and
+ * per giant step A(i) [2][k][n], the special prime's row of A(i)_1 [n], v(i) [L][n] and E(i) [L][k][n].  Every giant step of every ciphertext
+ * of the call is in flight at once; a caller short of memory splits the batch.
+ * An identity giant step takes its row of v and E in the scratch and its share of the drop and digit launches although nothing reads them
+ * (rows are not compacted): with G2 = 1 and h = {1} the call costs fhe_rotate_diag_sum_sp's work plus four launches and L k + L + 1
+ * transforms per ciphertext -- use fhe_rotate_diag_sum_sp for that case.
+ * The plan itself holds (pairs + 1) k n words on the device for `pairs` present pairs (plan creation stages the same amount on the host):
+ * 64 MiB for 16 x 16 pairs and 1 GiB for a dense 64 x 64 plan at n = 8192, k = 4.
+ * In place: out2 == ct2 with equal strides is allowed; every other overlap is refused.
+ * Refused (FHE_ERR_PARAM) before anything is enqueued: everything fhe_rotdiag_plan_create / fhe_rotate_diag_sum_sp refuse, G1 or G2 of 0 or
+ * above 64, a repeated element within a list, a giant step with no present pair, a baby step with no present pair (a key demanded for
+ * nothing), a plaintext coefficient >= t, a null key for a non-identity element, scratch_bytes < fhe_rotbsgs_scratch_bytes(plan, count).
+ * count == 0 is a no-op. */
+typedef struct fhe_rotbsgs_plan fhe_rotbsgs_plan;
+int fhe_rotbsgs_plan_create(const fhe_ctx *ctx, uint32_t G1, const uint32_t *baby_elts, uint32_t G2, const uint32_t *giant_elts,
+                            const uint64_t *plains_host, const uint64_t *const *d_baby_keys_ntt, const uint64_t *const *d_giant_keys_ntt,
+                            fhe_rotbsgs_plan **out);
+int fhe_rotbsgs_plan_destroy(fhe_rotbsgs_plan *plan);
+size_t fhe_rotbsgs_scratch_bytes(const fhe_rotbsgs_plan *plan, uint64_t count);
+int fhe_rotate_bsgs_sp(const fhe_rotbsgs_plan *plan, const uint64_t *ct2, uint64_t ct_stride_words, uint64_t *out2, uint64_t out_stride_words,
+                       uint64_t count, void *scratch, size_t scratch_bytes, fhe_stream stream);
 
 /* ---- fused block circuit: encrypted_dct (homo/fhe_image.h:196-288) followed by quantize_fhe
  * (homo/fhe_image.h:294-305) on n_blocks independent 8x8 blocks.  in/out: [n_blocks][64][2][k][n].
