@@ -1,6 +1,6 @@
 // rotbsgs_host.h -- the host arithmetic a baby-step / giant-step plan adds to rotdiag_host.h (rotbsgs.hip, include/fhe_hip.h
 // fhe_rotbsgs_plan_create): the checks on the two element lists, on the plaintexts [G2][G1][n] and their keys, the table of the present
-// pairs and the scratch formula.  The centred lift and the slot permutations are rotdiag_host.h's and rotsum_host.h's, as they are.
+// pairs and the scratch formula.  The centred lift, the slot permutations and the check on a call's operands are rotdiag_host.h's and rotsum_host.h's.
 // No device, no HIP header: tools/rotbsgs_host_check.cpp builds it alone, under the host sanitizers.
 #pragma once
 #include "rotdiag_host.h"

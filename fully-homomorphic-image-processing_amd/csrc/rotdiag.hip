@@ -13,16 +13,22 @@
 // and multiplies by p^-1 mod q_r.  The identity tap's c_1 term is [p]_(q_r) P_id,r (*) D_r,r in acc'_1,r in the same way.  The tail is then an
 // inverse transform and the drop, with no read of the input: every input word is in scratch before the first store, so out2 may be ct2.
 //
-// Pseudo-Mersenne bases, four launches whatever the number of taps:
-//   k_rd_fwd_pm        workgroup (c, i, r): k_ksp_fwd_pm's digit transforms of c_1, and (c, r < L): the transform of c_0,r
-//   k_rd_accum_pm      per (c, r, slot): per tap L gathered digits against both key polynomials plus the gathered C0 word against [p]_(q_r),
-//                      folded, times P_j,r[slot]; lazy sum over taps
-//   k_ksp_inv_sp_pm    (keyswitch_sp.hip)
-//   k_rd_inv_down_pm   workgroup (c, pp, r < L): inverse transform, the drop, the store
-// General path (FP64-transform bases, 61-bit primes, FHE_NTT_NOPM=1): element-wise Barrett kernels around fhe_qbase_ntt.  Every quantity is
-// the canonical residue of the same integer on both paths: the same bits.
+// The steps of a call, on either path:
+//   fhe_rot_forward    the digit transforms of c_1 and the transform of c_0
+//   k_rd_accum         per (c, r, slot): per tap L gathered digits against both key polynomials plus the gathered C0 word against [p]_(q_r)
+//                      (rotdiag_core.h's rot_tap_term), times P_j,r[slot]; the sum over taps
+//   fhe_rot_drop       inverse transform, the drop, the store
+// Pseudo-Mersenne bases, four launches whatever the number of taps: k_rd_fwd_pm (workgroup (c, i, r): k_ksp_fwd_pm's digit transforms of
+// c_1, and (c, r < L): the transform of c_0,r), k_rd_accum<ArPm<C>> (lazy sums), k_ksp_inv_sp_pm (keyswitch_sp.hip), k_rd_inv_down_pm.
+// General path (FP64-transform bases, 61-bit primes, FHE_NTT_NOPM=1), seven: k_rd_stage_c0, the base's transform and fhe_ksp_forward;
+// k_rd_accum<ArBarrett>; fhe_qbase_ntt and k_rd_down.  Every quantity is the canonical residue of the same integer on both paths: the
+// same bits.
+// This file also defines, once, what rotdiag_core.h declares for rotbsgs.hip and rotsum.hip: the forward and the drop step with their
+// kernels and dispatches, and the two halves of plan creation (the slot exponents from the transform of X; the permutation and key tables).
 #include "rotdiag_core.h"
 #include "rotdiag_host.h"
+
+#include <memory>
 
 struct fhe_rotdiag_plan {
     const fhe_ctx *ctx = nullptr;
@@ -32,6 +38,9 @@ struct fhe_rotdiag_plan {
     u64 *d_P = nullptr;
     u32 *d_perm = nullptr;
     const u64 **d_keys = nullptr;
+    ~fhe_rotdiag_plan() {
+        if (d_block) (void)hipFree(d_block);
+    }
 };
 
 namespace {
@@ -44,19 +53,12 @@ struct RdTaps {
     u32 taps;
 };
 
-// rotsum.hip's lazy tap sum (a term is a mulvv_pm result below RQ / 16 q, folded every RD_FOLD_TAPS terms), with one more term in the sum of
-// a tap: the L digit products and the C0 product, L + 1 <= FHE_MAX_K terms below RQ each in 64 bits (48 q of 512 on class A, 12 q of 64 on
-// class B).  The diagonal word P_j,r[s] is canonical, as the scalar weight was: the product bound RQ is the same.
-constexpr int RD_FOLD_TAPS = 32;
-template <typename C> constexpr bool rd_bounds_ok() {
-    return PM_FOLDED + RD_FOLD_TAPS * C::RQ <= 4 * C::LIM        // a folded sum and RD_FOLD_TAPS more terms fit 64 bits
-           && FHE_MAX_K * C::RQ <= 4 * C::LIM                    // the L + 1 <= 8 products of one tap do
-           && PM_FOLDED <= 32;                                   // a folded value is a valid first operand of mulvv_pm (below 2^(b+1))
-}
-static_assert(rd_bounds_ok<PmA>() && rd_bounds_ok<PmB>(), "lazy tap sums");
+// The lazy tap sum of the pseudo-Mersenne path is rotdiag_core.h's (rot_bounds_ok): per tap the L digit products and the C0 product, L + 1 <=
+// FHE_MAX_K terms below RQ each in 64 bits (48 q of 512 on class A, 12 q of 64 on class B), one fold, and the product with the canonical
+// diagonal word P_j,r[s], below RQ again; the sum over taps is folded every ROT_FOLD_TERMS products.
 
-// ---- general path -------------------------------------------------------------------------------------------------------------------
-// c0h [count][k][n]: c_0,r for r < L, zeros at the special prime, for the base's own forward transforms
+// ---- the shared steps (rotdiag_core.h) --------------------------------------------------------------------------------------------------
+// general path: c0h [count][k][n] = c_0,r for r < L, zeros at the special prime, for the base's own forward transforms
 __global__ __launch_bounds__(256) void k_rd_stage_c0(const u64 *__restrict__ ct, u64 stride, u64 *__restrict__ c0h, u32 k, u32 n, u64 count) {
     for (u64 u = blockIdx.y; u < count * k; u += gridDim.y) {
         const u32 r = (u32)(u % k);
@@ -65,106 +67,97 @@ __global__ __launch_bounds__(256) void k_rd_stage_c0(const u64 *__restrict__ ct,
         for (u32 x = blockIdx.x * blockDim.x + threadIdx.x; x < n; x += gridDim.x * blockDim.x) c0h[u * n + x] = r < k - 1 ? src[x] : 0;
     }
 }
-// acc[c][pp][r][s] = sum_j P_j,r[s] (sum_i dig[c][i][r][perm_j[s]] key_j[i][pp][r][s] + [p]_(q_r) (pp = 0: c0h[c][r][perm_j[s]]; pp = 1 and
-// g_j = 1: dig[c][r][r][s])), canonical Barrett products
-__global__ __launch_bounds__(256) void k_rd_accum(const u64 *__restrict__ dig, const u64 *__restrict__ c0h, RdTaps P, u64 *__restrict__ acc,
-                                                  const Modulus *__restrict__ mod, u32 k, u32 n, u64 count) {
+// general path: acc [rows][k][n] in coefficient form -> the drop of the special prime; row = c * 2 + pp goes to out + c * out_stride + (pp L + r) n
+__global__ __launch_bounds__(256) void k_rd_down(u64 *__restrict__ out, u64 out_stride, const u64 *__restrict__ acc, KspTab T, u32 k, u32 n, u64 rows) {
     const u32 Lq = k - 1;
-    for (u64 u = blockIdx.y; u < count * k; u += gridDim.y) {
-        const u32 r = (u32)(u % k);
-        const u64 c = u / k;
-        const Modulus m = mod[r];
-        const bool low = r < Lq;
-        const u64 pr = P.pr[r];
-        for (u32 s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
-            u64 s0 = 0, s1 = 0;
-            for (u32 j = 0; j < P.taps; j++) {
-                const u64 *key = P.keys[j];
-                const u32 src = P.perm[(u64)j * n + s];
-                u64 a0 = 0, a1 = 0;
-                if (key) {
-                    for (u32 i = 0; i < Lq; i++) {
-                        const u64 x = dig[((c * Lq + i) * k + r) * n + src];
-                        const u64 *e = key + (((u64)i * 2) * k + r) * n + s;
-                        a0 = addmod(a0, mul_barrett(x, e[0], m), m.q);
-                        a1 = addmod(a1, mul_barrett(x, e[(u64)k * n], m), m.q);
-                    }
-                }
-                if (low) {
-                    a0 = addmod(a0, mul_barrett(c0h[(c * k + r) * n + src], pr, m), m.q);
-                    if (!key) a1 = mul_barrett(dig[((c * Lq + r) * k + r) * n + src], pr, m);
-                }
-                const u64 w = P.P[((u64)j * k + r) * n + s];
-                s0 = addmod(s0, mul_barrett(a0, w, m), m.q);
-                s1 = addmod(s1, mul_barrett(a1, w, m), m.q);
-            }
-            acc[((c * 2 + 0) * k + r) * n + s] = s0;
-            acc[((c * 2 + 1) * k + r) * n + s] = s1;
-        }
-    }
-}
-// acc in coefficient form: the drop of the special prime
-__global__ __launch_bounds__(256) void k_rd_down(u64 *__restrict__ out, u64 out_stride, const u64 *__restrict__ acc, KspTab T, u32 k, u32 n, u64 count) {
-    const u32 Lq = k - 1;
-    for (u64 u = blockIdx.y; u < count * 2 * Lq; u += gridDim.y) {
-        const u32 r = (u32)(u % Lq), pp = (u32)((u / Lq) & 1);
-        const u64 c = u / (2 * Lq);
-        const u64 *a = acc + ((c * 2 + pp) * k + r) * n, *ap = acc + ((c * 2 + pp) * k + Lq) * n;
-        u64 *dst = out + c * out_stride + ((u64)pp * Lq + r) * n;
+    for (u64 u = blockIdx.y; u < rows * Lq; u += gridDim.y) {
+        const u32 r = (u32)(u % Lq);
+        const u64 row = u / Lq;
+        const u64 *a = acc + (row * k + r) * n, *ap = acc + (row * k + Lq) * n;
+        u64 *dst = out + (row >> 1) * out_stride + ((row & 1) * Lq + r) * n;
         for (u32 j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) dst[j] = ksp_drop(a[j], ap[j], T, r);
     }
 }
+// pseudo-Mersenne path, per ciphertext L k + L workgroups.  The first L k are k_ksp_fwd_pm's (c, i, r): dig[c][i][r] = NTT_(q_r)([c_1,i]_(q_r)),
+// folded below PM_FOLDED when r != i.  The last L are (c, r): c0h[c][r] = NTT_(q_r)(c_0,r), canonical input.
+template <int L, typename C>
+__global__ __launch_bounds__(NttShape<L>::TP, 4) void k_rd_fwd_pm(const u64 *__restrict__ ct, u64 stride, u64 *__restrict__ dig, u64 *__restrict__ c0h, RnsBase base) {
+    __shared__ u64 lds[NttShape<L>::LDS_WORDS];
+    constexpr int N = NttShape<L>::N;
+    const int tid = threadIdx.x;
+    const u32 k = base.count, Lq = k - 1, per = Lq * k + Lq, w = blockIdx.x % per;
+    const u64 c = blockIdx.x / per;
+    const bool d = w < Lq * k;                     // uniform per workgroup
+    const u32 r = d ? w % k : w - Lq * k, i = d ? w / k : r;
+    const PmMod m = base.pm[r];
+    u64 x[1][16];
+    load_coeff<L>(x[0], ct + c * stride + ((u64)(d ? Lq : 0) + i) * N, tid);
+    if (r != i) {
+#pragma unroll
+        for (int e = 0; e < 16; e++) x[0][e] = fold_pm(x[0][e], m);
+    }
+    ntt_fwd_regs_pm<L, 1, PM_FOLDED, C::LIM, C::CS>(x, base.tw_pm + (size_t)r * N, m, lds, tid);
+#pragma unroll
+    for (int e = 0; e < 16; e++) x[0][e] = canon_pm(x[0][e], m);
+    store_slots<L>(x[0], d ? dig + ((c * Lq + i) * k + r) * N : c0h + (c * k + r) * N, tid);
+}
+// pseudo-Mersenne path, workgroup (row = c * 2 + pp, r < L): k_ksp_inv_down_add_pm's transform and drop, nothing added: the input's terms
+// went through the accumulator
+template <int L, typename C>
+__global__ __launch_bounds__(NttShape<L>::TP, 4) void k_rd_inv_down_pm(u64 *__restrict__ out, u64 out_stride, const u64 *__restrict__ acc, const u64 *__restrict__ sp,
+                                                                        RnsBase base, KspTab T) {
+    __shared__ u64 lds[NttShape<L>::LDS_WORDS];
+    constexpr int N = NttShape<L>::N;
+    const int tid = threadIdx.x;
+    const u32 k = base.count, Lq = k - 1, r = blockIdx.x % Lq, pp = (blockIdx.x / Lq) & 1;
+    const u64 cpp = blockIdx.x / Lq;               // c * 2 + pp
+    const u64 c = cpp >> 1;
+    const PmMod m = base.pm[r];
+    u64 x[1][16], y[16];
+    load_slots<L>(x[0], acc + (cpp * k + r) * N, tid);
+    ntt_inv_regs_pm<L, 1, PM_FOLDED, C::XB, C::LIM, C::RQ>(x, base.itw_pm + (size_t)r * N, m, lds, tid);
+    load_coeff<L>(y, sp + cpp * N, tid);
+#pragma unroll
+    for (int e = 0; e < 16; e++) x[0][e] = ksp_drop(canon_rq_pm<C::RQ>(x[0][e], m), y[e], T, r);
+    store_coeff<L>(x[0], out + c * out_stride + ((u64)pp * Lq + r) * N, tid);
+}
 
-// ---- pseudo-Mersenne path -------------------------------------------------------------------------------------------------------------
-// (1) k_rd_fwd_pm (rotdiag_core.h)
-// (2) per (c, r, slot).  Per tap: k_rs_accum_pm's L gathered digits against both key polynomials, and for r < L the gathered C0 word (pp = 0)
-// or, on the identity tap, D_r,r (pp = 1) against the canonical [p]_(q_r): at most L + 1 <= 8 mulvv_pm terms below RQ each in a 64-bit sum
-// (rd_bounds_ok); one fold (below PM_FOLDED / 16 q < 2^(b+1): a valid first operand of mulvv_pm); the product with the canonical P_j,r[s] is
-// below RQ again.  The sum over taps holds a folded value and at most RD_FOLD_TAPS such products.
-template <typename C>
-__global__ __launch_bounds__(256) void k_rd_accum_pm(const u64 *__restrict__ dig, const u64 *__restrict__ c0h, RdTaps P, u64 *__restrict__ acc, RnsBase base,
-                                                     u32 n, u64 count) {
-    const u32 k = base.count, Lq = k - 1;
+// ---- the accumulation, one kernel for both paths ----------------------------------------------------------------------------------------
+// acc[c][pp][r][s] = sum_j P_j,r[s] T_j,pp,r[s] per (c, r, slot), T_j rot_tap_term's.  ArBarrett: canonical residues throughout, the folds
+// and their counter vanish.  ArPm: T_j is folded once (below PM_FOLDED / 16 q < 2^(b+1): a valid first operand of mulvv_pm), the product
+// with the canonical P_j,r[s] is below RQ again, and the sum over taps holds a folded value and at most ROT_FOLD_TERMS such products.
+template <typename A>
+__global__ __launch_bounds__(256) void k_rd_accum(const u64 *__restrict__ dig, const u64 *__restrict__ c0h, RdTaps P, u64 *__restrict__ acc, typename A::Tab tab,
+                                                  u32 k, u32 n, u64 count) {
+    const u32 Lq = k - 1;
+    const u32 kn = k * n;
     for (u64 u = blockIdx.y; u < count * k; u += gridDim.y) {
         const u32 r = (u32)(u % k);
         const u64 c = u / k;
-        const PmMod m = base.pm[r];
-        const bool low = r < Lq;
+        const typename A::Mod m = A::mod(tab, r);
         const u64 pr = P.pr[r];
+        const u64 *dr = dig + c * Lq * kn + (u64)r * n, *c0r = c0h + u * n;
         for (u32 s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
             u64 s0 = 0, s1 = 0;
             u32 since = 0;
             for (u32 j = 0; j < P.taps; j++) {
                 const u64 *key = P.keys[j];
-                const u32 src = P.perm[(u64)j * n + s];
-                u64 a0 = 0, a1 = 0;
-                if (key) {                                             // uniform: every tap but the one with g = 1
-                    for (u32 i = 0; i < Lq; i++) {
-                        const u64 x = dig[((c * Lq + i) * k + r) * n + src];
-                        const u64 *e = key + (((u64)i * 2) * k + r) * n + s;
-                        a0 += mulvv_pm(x, e[0], m);
-                        a1 += mulvv_pm(x, e[(u64)k * n], m);
-                    }
-                }
-                if (low) {                                             // uniform per row
-                    a0 += mulvv_pm(c0h[(c * k + r) * n + src], pr, m);
-                    if (!key) a1 = mulvv_pm(dig[((c * Lq + r) * k + r) * n + src], pr, m);
-                }
+                u64 a0, a1;
+                rot_tap_term<A>(dr, c0r, key ? key + (u64)r * n + s : nullptr, P.perm[(u64)j * n + s], r, Lq, kn, pr, m, a0, a1);
                 const u64 w = P.P[((u64)j * k + r) * n + s];
-                s0 += mulvv_pm(fold_pm(a0, m), w, m);
-                s1 += mulvv_pm(fold_pm(a1, m), w, m);
-                if (++since == RD_FOLD_TAPS) {
-                    s0 = fold_pm(s0, m);
-                    s1 = fold_pm(s1, m);
+                s0 = A::add(s0, A::mul(A::fold(a0, m), w, m), m);
+                s1 = A::add(s1, A::mul(A::fold(a1, m), w, m), m);
+                if (++since == ROT_FOLD_TERMS) {
+                    s0 = A::fold(s0, m);
+                    s1 = A::fold(s1, m);
                     since = 0;
                 }
             }
-            acc[((c * 2 + 0) * k + r) * n + s] = fold_pm(s0, m);
-            acc[((c * 2 + 1) * k + r) * n + s] = fold_pm(s1, m);
+            acc[((c * 2 + 0) * k + r) * n + s] = A::fold(s0, m);
+            acc[((c * 2 + 1) * k + r) * n + s] = A::fold(s1, m);
         }
     }
 }
-// (4) k_rd_inv_down_pm (rotdiag_core.h)
 
 // the digits [L][k][n], C0 [k][n] (the special prime's row is used by the general path alone), the accumulators [2][k][n] and the special
 // prime's coefficients [2][n] (pseudo-Mersenne path) per ciphertext
@@ -180,55 +173,77 @@ int run(const fhe_rotdiag_plan *p, const u64 *ct, u64 stride, u64 *out, u64 out_
     const KspTab T = ksp_tab(c);
     RdTaps P{p->d_perm, p->d_P, p->d_keys, {0}, p->taps};
     for (u32 r = 0; r < Lq; r++) P.pr[r] = T.p % T.q[r];
-    int rc;
-    if (fhe_ksp_pm_ok(c, count)) {
+    if (int rc = fhe_rot_forward(c, ct, stride, dig, c0h, count, st)) return rc;
+    const dim3 g2 = ksp_grid2(n, count * k);
+    if (!fhe_rot_pm(c)) k_rd_accum<ArBarrett><<<g2, 256, 0, st>>>(dig, c0h, P, acc, c->qb.d_mod, k, n, count);
+    else if (c->qb.pm_class == 1) k_rd_accum<ArPm<PmA>><<<g2, 256, 0, st>>>(dig, c0h, P, acc, c->qb.dev(), k, n, count);
+    else k_rd_accum<ArPm<PmB>><<<g2, 256, 0, st>>>(dig, c0h, P, acc, c->qb.dev(), k, n, count);
+    KERNEL_CHECK();
+    return fhe_rot_drop(c, acc, sp, out, out_stride, count * 2, st);
+}
+
+}  // namespace
+
+int fhe_rot_forward(const fhe_ctx *c, const u64 *ct, u64 stride, u64 *dig, u64 *c0h, u64 count, hipStream_t st) {
+    const u32 k = c->k, Lq = k - 1;
+    if (fhe_rot_pm(c)) {
         const RnsBase base = c->qb.dev();
-        const unsigned g1 = (unsigned)(count * (Lq * k + Lq)), g4 = (unsigned)(count * 2 * Lq);
-        const dim3 g2 = ksp_grid2(n, count * k);
-        if (c->qb.pm_class == 1) {
-            DISPATCH_L(c->logn, (k_rd_fwd_pm<L, PmA><<<g1, NttShape<L>::TP, 0, st>>>(ct, stride, dig, c0h, base)));
-            k_rd_accum_pm<PmA><<<g2, 256, 0, st>>>(dig, c0h, P, acc, base, n, count);
-        } else {
-            DISPATCH_L(c->logn, (k_rd_fwd_pm<L, PmB><<<g1, NttShape<L>::TP, 0, st>>>(ct, stride, dig, c0h, base)));
-            k_rd_accum_pm<PmB><<<g2, 256, 0, st>>>(dig, c0h, P, acc, base, n, count);
-        }
+        const unsigned g1 = (unsigned)(count * (Lq * k + Lq));
+        if (c->qb.pm_class == 1) { DISPATCH_L(c->logn, (k_rd_fwd_pm<L, PmA><<<g1, NttShape<L>::TP, 0, st>>>(ct, stride, dig, c0h, base))); }
+        else { DISPATCH_L(c->logn, (k_rd_fwd_pm<L, PmB><<<g1, NttShape<L>::TP, 0, st>>>(ct, stride, dig, c0h, base))); }
         KERNEL_CHECK();
-        if ((rc = fhe_ksp_inv_sp(c, acc, sp, count * 2, st))) return rc;
+        return FHE_OK;
+    }
+    k_rd_stage_c0<<<ksp_grid2(c->n, count * k), 256, 0, st>>>(ct, stride, c0h, k, c->n, count);
+    KERNEL_CHECK();
+    if (int rc = fhe_qbase_ntt(false, c, c0h, c0h, count, st)) return rc;
+    return fhe_ksp_forward(c, ct, stride, 1, dig, count, st);
+}
+
+int fhe_rot_drop(const fhe_ctx *c, u64 *acc, u64 *sp, u64 *out, u64 out_stride, u64 rows, hipStream_t st) {
+    const u32 k = c->k, Lq = k - 1;
+    const KspTab T = ksp_tab(c);
+    if (fhe_rot_pm(c)) {
+        const RnsBase base = c->qb.dev();
+        const unsigned g4 = (unsigned)(rows * Lq);
+        if (int rc = fhe_ksp_inv_sp(c, acc, sp, rows, st)) return rc;
         if (c->qb.pm_class == 1) { DISPATCH_L(c->logn, (k_rd_inv_down_pm<L, PmA><<<g4, NttShape<L>::TP, 0, st>>>(out, out_stride, acc, sp, base, T))); }
         else { DISPATCH_L(c->logn, (k_rd_inv_down_pm<L, PmB><<<g4, NttShape<L>::TP, 0, st>>>(out, out_stride, acc, sp, base, T))); }
         KERNEL_CHECK();
         return FHE_OK;
     }
-    k_rd_stage_c0<<<ksp_grid2(n, count * k), 256, 0, st>>>(ct, stride, c0h, k, n, count);
-    KERNEL_CHECK();
-    if ((rc = fhe_qbase_ntt(false, c, c0h, c0h, count, st))) return rc;
-    if ((rc = fhe_ksp_forward(c, ct, stride, 1, dig, count, st))) return rc;
-    k_rd_accum<<<ksp_grid2(n, count * k), 256, 0, st>>>(dig, c0h, P, acc, c->qb.d_mod, k, n, count);
-    KERNEL_CHECK();
-    if ((rc = fhe_qbase_ntt(true, c, acc, acc, count * 2, st))) return rc;
-    k_rd_down<<<ksp_grid2(n, count * 2 * Lq), 256, 0, st>>>(out, out_stride, acc, T, k, n, count);
+    if (int rc = fhe_qbase_ntt(true, c, acc, acc, rows, st)) return rc;
+    k_rd_down<<<ksp_grid2(c->n, rows * Lq), 256, 0, st>>>(out, out_stride, acc, T, k, c->n, rows);
     KERNEL_CHECK();
     return FHE_OK;
 }
 
-// in the order include/fhe_hip.h lists them (fhe_rotate_sum_sp's)
-int check_call(const fhe_rotdiag_plan *p, const void *ct, u64 stride, const void *out, u64 out_stride, u64 count, const void *scratch, size_t scratch_bytes) {
-    const fhe_ctx *c = p->ctx;
-    const u64 Ln = (u64)(c->k - 1) * c->n;
-    if (stride < 2 * Ln) return fail(FHE_ERR_PARAM, "ciphertext stride smaller than a size-2 ciphertext of %u primes", c->k - 1);
-    if (out_stride < 2 * Ln) return fail(FHE_ERR_PARAM, "output stride smaller than a size-2 ciphertext of %u primes", c->k - 1);
-    if (!count) return FHE_OK;
-    if (count * c->k * c->k > 0x7fffffffULL) return fail(FHE_ERR_PARAM, "too many ciphertexts for one call");
-    const size_t need = scratch_words(p, count) * sizeof(u64);
-    if (!scratch || scratch_bytes < need) return fail(FHE_ERR_PARAM, "scratch too small");
-    const u64 in_words = (count - 1) * stride + 2 * Ln, out_words = (count - 1) * out_stride + 2 * Ln;
-    if (!(out == ct && out_stride == stride) && overlap(ct, in_words, out, out_words))
-        return fail(FHE_ERR_PARAM, "output range overlaps the input range (only out2 == ct2 with out_stride == stride may alias)");
-    if (overlap(scratch, need / 8, ct, in_words) || overlap(scratch, need / 8, out, out_words)) return fail(FHE_ERR_PARAM, "scratch overlaps the input or the output");
+int fhe_rot_slot_exponents(const fhe_ctx *c, u64 *d, u32 rows, const char *what, std::vector<u32> &f) {
+    const u32 n = c->n, k = c->k;
+    const size_t row = (size_t)k * n;
+    std::vector<uint64_t> x(row, 0);
+    for (u32 r = 0; r < k; r++) x[(size_t)r * n + 1] = 1;
+    if (hipMemcpy(d + rows * row, x.data(), row * 8, hipMemcpyHostToDevice) != hipSuccess) return fail(FHE_ERR_HIP, "upload of %s", what);
+    if (int rc = fhe_qbase_ntt(false, c, d, d, rows + 1, nullptr)) return rc;
+    if (hipStreamSynchronize(nullptr) != hipSuccess || hipMemcpy(x.data(), d + rows * row, row * 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(FHE_ERR_HIP, "transform of %s", what);
+    // slot s of the transform of X holds psi_r^(e_s)
+    std::vector<u32> fr;
+    if (!rotsum::slot_exponents(x.data(), n, c->qb.primes[0], f)) return fail(FHE_ERR_PARAM, "the context's transform of X is not a set of odd powers of one root");
+    for (u32 r = 1; r < k; r++)
+        if (!rotsum::slot_exponents(x.data() + (size_t)r * n, n, c->qb.primes[r], fr) || fr != f)
+            return fail(FHE_ERR_PARAM, "the context's transforms order their slots differently from prime to prime");
     return FHE_OK;
 }
 
-}  // namespace
+int fhe_rot_perm_keys(const std::vector<u32> &f, u32 count, const u32 *elts, const uint64_t *const *d_keys, u32 *perm, u64 *keys) {
+    for (u32 j = 0; j < count; j++) {
+        const u32 g = elts[j];
+        if (!rotsum::slot_perm(f, g, perm + j * f.size())) return fail(FHE_ERR_PARAM, "no slot permutation for Galois element %u", g);
+        keys[j] = g == 1 ? 0 : (u64)(uintptr_t)d_keys[j];
+    }
+    return FHE_OK;
+}
 
 extern "C" int fhe_rotdiag_plan_create(const fhe_ctx *c, uint32_t taps, const uint32_t *elts, const uint64_t *plains, const uint64_t *const *d_keys,
                                        fhe_rotdiag_plan **out) {
@@ -238,58 +253,37 @@ extern "C" int fhe_rotdiag_plan_create(const fhe_ctx *c, uint32_t taps, const ui
     std::string why = rotsum::check_taps(n, c->t, k, taps, elts, ones.data(), (const void *const *)d_keys);
     if (why.empty()) why = rotdiag::check_plains(n, c->t, taps, plains);
     if (!why.empty()) return fail(FHE_ERR_PARAM, "%s", why.c_str());
-    // rows 0 .. taps - 1: the centred lifts; row taps: the monomial X.  One run of the context's own forward transform: slot s of X holds psi_r^(e_s)
+    // rows 0 .. taps - 1 of the block: the centred lifts, transformed with the row of X behind them (fhe_rot_slot_exponents); the block is sized
+    // for that, and the permutations and the keys then take the place of the row of X and what follows
     const size_t row = (size_t)k * n, b_P = (size_t)taps * row * 8, b_perm = (((size_t)taps * n * 4) + 7) & ~(size_t)7, b_keys = (size_t)taps * 8;
-    std::vector<uint64_t> h((taps + 1) * row, 0);
+    std::vector<uint64_t> h(taps * row, 0);
     const std::vector<uint64_t> primes(c->qb.primes.begin(), c->qb.primes.end());
     for (u32 j = 0; j < taps; j++) rotdiag::lift(plains + (size_t)j * n, n, c->t, primes.data(), k, h.data() + j * row);
-    for (u32 r = 0; r < k; r++) h[taps * row + (size_t)r * n + 1] = 1;
-    fhe_rotdiag_plan *p = new fhe_rotdiag_plan;
+    std::unique_ptr<fhe_rotdiag_plan> p(new fhe_rotdiag_plan);
     p->ctx = c;
     p->taps = taps;
     p->elts.assign(elts, elts + taps);
-    auto bail = [&](int rc) {
-        if (p->d_block) (void)hipFree(p->d_block);
-        delete p;
-        return rc;
-    };
-    // the block is sized for the transform's input (taps + 1 rows); the permutations and the keys then take the place of the row of X and what follows
     const size_t bytes = b_P + (row * 8 > b_perm + b_keys ? row * 8 : b_perm + b_keys);
     if (hipMalloc(&p->d_block, bytes) != hipSuccess) {
         p->d_block = nullptr;
-        return bail(fail(FHE_ERR_NOMEM, "device allocation of %zu bytes for the rotate-diag plan", bytes));
+        return fail(FHE_ERR_NOMEM, "device allocation of %zu bytes for the rotate-diag plan", bytes);
     }
     u64 *d = (u64 *)p->d_block;
-    if (hipMemcpy(d, h.data(), h.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return bail(fail(FHE_ERR_HIP, "upload of the plaintexts"));
-    if (int rc = fhe_qbase_ntt(false, c, d, d, taps + 1, nullptr)) return bail(rc);
-    std::vector<uint64_t> x(row);
-    if (hipStreamSynchronize(nullptr) != hipSuccess || hipMemcpy(x.data(), d + taps * row, row * 8, hipMemcpyDeviceToHost) != hipSuccess)
-        return bail(fail(FHE_ERR_HIP, "transform of the plaintexts"));
-    std::vector<u32> f, fr;
-    if (!rotsum::slot_exponents(x.data(), n, c->qb.primes[0], f)) return bail(fail(FHE_ERR_PARAM, "the context's transform of X is not a set of odd powers of one root"));
-    for (u32 r = 1; r < k; r++)
-        if (!rotsum::slot_exponents(x.data() + (size_t)r * n, n, c->qb.primes[r], fr) || fr != f)
-            return bail(fail(FHE_ERR_PARAM, "the context's transforms order their slots differently from prime to prime"));
+    if (hipMemcpy(d, h.data(), b_P, hipMemcpyHostToDevice) != hipSuccess) return fail(FHE_ERR_HIP, "upload of the plaintexts");
+    std::vector<u32> f;
+    if (int rc = fhe_rot_slot_exponents(c, d, taps, "the plaintexts", f)) return rc;
     std::vector<unsigned char> tail(b_perm + b_keys, 0);
-    u32 *perm = (u32 *)tail.data();
-    u64 *keys = (u64 *)(tail.data() + b_perm);
-    for (u32 j = 0; j < taps; j++) {
-        const u32 g = elts[j];
-        if (!rotsum::slot_perm(f, g, perm + (size_t)j * n)) return bail(fail(FHE_ERR_PARAM, "no slot permutation for Galois element %u", g));
-        keys[j] = g == 1 ? 0 : (u64)(uintptr_t)d_keys[j];
-    }
+    if (int rc = fhe_rot_perm_keys(f, taps, elts, d_keys, (u32 *)tail.data(), (u64 *)(tail.data() + b_perm))) return rc;
     if (hipMemcpy((unsigned char *)p->d_block + b_P, tail.data(), tail.size(), hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(FHE_ERR_HIP, "upload of the rotate-diag plan"));
+        return fail(FHE_ERR_HIP, "upload of the rotate-diag plan");
     p->d_P = d;
     p->d_perm = (u32 *)((unsigned char *)p->d_block + b_P);
     p->d_keys = (const u64 **)((unsigned char *)p->d_block + b_P + b_perm);
-    *out = p;
+    *out = p.release();
     return FHE_OK;
 }
 
 extern "C" int fhe_rotdiag_plan_destroy(fhe_rotdiag_plan *p) {
-    if (!p) return FHE_OK;
-    if (p->d_block) (void)hipFree(p->d_block);
     delete p;
     return FHE_OK;
 }
@@ -302,7 +296,9 @@ extern "C" size_t fhe_rotdiag_scratch_bytes(const fhe_rotdiag_plan *p, uint64_t 
 extern "C" int fhe_rotate_diag_sum_sp(const fhe_rotdiag_plan *p, const uint64_t *ct2, uint64_t stride, uint64_t *out2, uint64_t out_stride, uint64_t count,
                                       void *scratch, size_t scratch_bytes, fhe_stream s) {
     if (!p || !ct2 || !out2) return fail(FHE_ERR_PARAM, "null argument");
-    if (int rc = check_call(p, ct2, stride, out2, out_stride, count, scratch, scratch_bytes)) return rc;
+    const fhe_ctx *c = p->ctx;
+    const std::string why = rotsum::check_call(c->k, c->n, ct2, stride, out2, out_stride, count, count * c->k * c->k, scratch_words(p, count) * sizeof(u64), scratch, scratch_bytes);
+    if (!why.empty()) return fail(FHE_ERR_PARAM, "%s", why.c_str());
     if (!count) return FHE_OK;
     return run(p, (const u64 *)ct2, stride, (u64 *)out2, out_stride, count, (u64 *)scratch, (hipStream_t)s);
 }

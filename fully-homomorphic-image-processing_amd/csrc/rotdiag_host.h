@@ -1,6 +1,6 @@
 // rotdiag_host.h -- the host arithmetic a rotate-diag plan adds to rotsum_host.h (rotdiag.hip, include/fhe_hip.h fhe_rotdiag_plan_create):
-// the checks on the plaintexts and their centred lift to every prime.  The checks on the elements and keys and the slot permutations are
-// rotsum_host.h's, as they are.  No device, no HIP header: tools/rotdiag_host_check.cpp builds it alone, under the host sanitizers.
+// the checks on the plaintexts and their centred lift to every prime.  The checks on the elements and keys, the slot permutations and the
+// check on a call's operands are rotsum_host.h's.  No device, no HIP header: tools/rotdiag_host_check.cpp builds it alone, under the host sanitizers.
 #pragma once
 #include "rotsum_host.h"
 

@@ -13,7 +13,8 @@
 //
 // Pseudo-Mersenne bases, four launches whatever the number of taps:
 //   k_ksp_fwd_pm<L, C, false>   src_poly = 1 (keyswitch_sp.hip)
-//   k_rs_accum_pm               per (c, r, slot): per tap L gathered digits against both key polynomials, folded, times w'_j,r; lazy sum over taps
+//   k_rs_accum_pm               per (c, r, slot): per tap L gathered digits against both key polynomials (rotdiag_core.h's rot_digit_sum,
+//                               the one rotdiag.hip and rotbsgs.hip use), folded, times w'_j,r; lazy sum over taps
 //   k_ksp_inv_sp_pm             (keyswitch_sp.hip)
 //   k_rs_final_pm               workgroup (c, pp, r < L): inverse transform, the drop, then c_0,r through LDS once and one gather per tap
 //                               (pp = 0) or w' c_1,r at the words it then writes (pp = 1): u never exists in memory
@@ -21,10 +22,13 @@
 // General path (FP64-transform bases, 61-bit primes, FHE_NTT_NOPM=1): element-wise kernels around fhe_qbase_ntt; sum_j w'_j sigma(c_0) and
 // w' c_1 are staged in scratch BEFORE anything is written (a block's gathered reads cross other blocks' writes when the call runs in
 // place).  Every quantity is the canonical residue of the same integer on both paths: the same bits.
-#include "ksp_core.h"
+// The call check is rotsum_host.h's, and the slot exponents and the permutation / key tables of the plan come from rotdiag_core.h's two
+// plan helpers: both are shared with rotdiag.hip and rotbsgs.hip.
+#include "rotdiag_core.h"
 #include "rotsum_host.h"
 
 #include <cstring>
+#include <memory>
 
 #include "host_math.h"
 
@@ -37,6 +41,9 @@ struct fhe_rotsum_plan {
     u32 *d_perm = nullptr, *d_ginv = nullptr;
     u64 *d_w = nullptr, *d_w1 = nullptr;
     const u64 **d_keys = nullptr;
+    ~fhe_rotsum_plan() {
+        if (d_block) (void)hipFree(d_block);
+    }
 };
 
 namespace {
@@ -58,13 +65,8 @@ struct RsTaps {
 // a term is at most 2^b - 1 and 64 unfolded terms at most 2^64 - 64: with real products the unfolded sum would not wrap on a 58-bit prime
 // either (tests/test_rotsum_cpu.py reaches 0.999999 * 2^64 with every term crafted above q, and shows the wrap with the terms AT RQ).  The
 // fold stays because the kernel's ranges are proved from the checked bounds, not from that finer argument.
-constexpr int RS_FOLD_TAPS = 32;
-template <typename C> constexpr bool rs_bounds_ok() {
-    return PM_FOLDED + RS_FOLD_TAPS * C::RQ <= 4 * C::LIM        // a folded sum and RS_FOLD_TAPS more terms fit 64 bits
-           && (FHE_MAX_K - 1) * C::RQ <= 4 * C::LIM              // the L <= 7 digit products of one tap do (k_ksp_accum_pm's sum)
-           && PM_FOLDED <= 32;                                   // a folded value is a valid first operand of mulvv_pm (below 2^(b+1))
-}
-static_assert(rs_bounds_ok<PmA>() && rs_bounds_ok<PmB>(), "lazy tap sums");
+// The conditions themselves are rot_bounds_ok (rotdiag_core.h), shared with rotdiag.hip and rotbsgs.hip; this file's own is the last one.
+constexpr int RS_FOLD_TAPS = ROT_FOLD_TERMS;
 static_assert(PM_FOLDED + rotsum::MAX_TAPS * PmB::RQ > 4 * PmB::LIM, "class B: the fold every RS_FOLD_TAPS taps is what keeps 64 taps inside 64 bits");
 
 // ---- general path -------------------------------------------------------------------------------------------------------------------
@@ -90,23 +92,19 @@ __global__ __launch_bounds__(256) void k_rs_stage(const u64 *__restrict__ ct, u6
 __global__ __launch_bounds__(256) void k_rs_accum(const u64 *__restrict__ dig, RsTaps P, u64 *__restrict__ acc, const Modulus *__restrict__ mod, u32 k, u32 n,
                                                   u64 count, u32 j0, u32 j1) {
     const u32 Lq = k - 1;
+    const u32 kn = k * n;
     for (u64 u = blockIdx.y; u < count * k; u += gridDim.y) {
         const u32 r = (u32)(u % k);
         const u64 c = u / k;
         const Modulus m = mod[r];
+        const u64 *dr = dig + c * Lq * kn + (u64)r * n;
         for (u32 s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
             u64 s0 = 0, s1 = 0;
             for (u32 j = j0; j < j1; j++) {
                 const u64 *key = P.keys[j];
                 if (!key) continue;
-                const u32 src = P.perm[(u64)j * n + s];
                 u64 a0 = 0, a1 = 0;
-                for (u32 i = 0; i < Lq; i++) {
-                    const u64 x = dig[((c * Lq + i) * k + r) * n + src];
-                    const u64 *e = key + (((u64)i * 2) * k + r) * n + s;
-                    a0 = addmod(a0, mul_barrett(x, e[0], m), m.q);
-                    a1 = addmod(a1, mul_barrett(x, e[(u64)k * n], m), m.q);
-                }
+                rot_digit_sum<ArBarrett>(dr + P.perm[(u64)j * n + s], key + (u64)r * n + s, Lq, kn, m, a0, a1);
                 const u64 w = P.w[j * k + r];
                 s0 = addmod(s0, mul_barrett(a0, w, m), m.q);
                 s1 = addmod(s1, mul_barrett(a1, w, m), m.q);
@@ -143,10 +141,12 @@ __global__ __launch_bounds__(256) void k_rs_down_add(u64 *__restrict__ out, u64 
 template <typename C, bool EACH>
 __global__ __launch_bounds__(256) void k_rs_accum_pm(const u64 *__restrict__ dig, RsTaps P, u64 *__restrict__ acc, RnsBase base, u32 n, u64 count) {
     const u32 k = base.count, Lq = k - 1;
+    const u32 kn = k * n;
     for (u64 u = blockIdx.y; u < count * k; u += gridDim.y) {
         const u32 r = (u32)(u % k);
         const u64 c = u / k;
         const PmMod m = base.pm[r];
+        const u64 *dr = dig + c * Lq * kn + (u64)r * n;
         for (u32 s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
             u64 s0 = 0, s1 = 0;
             u32 since = 0;
@@ -154,14 +154,8 @@ __global__ __launch_bounds__(256) void k_rs_accum_pm(const u64 *__restrict__ dig
             for (u32 j = 0; j < P.taps; j++) {
                 const u64 *key = P.keys[j];
                 if (!key) continue;                                    // uniform: the tap with g = 1
-                const u32 src = P.perm[(u64)j * n + s];
                 u64 a0 = 0, a1 = 0;
-                for (u32 i = 0; i < Lq; i++) {
-                    const u64 x = dig[((c * Lq + i) * k + r) * n + src];
-                    const u64 *e = key + (((u64)i * 2) * k + r) * n + s;
-                    a0 += mulvv_pm(x, e[0], m);
-                    a1 += mulvv_pm(x, e[(u64)k * n], m);
-                }
+                rot_digit_sum<ArPm<C>>(dr + P.perm[(u64)j * n + s], key + (u64)r * n + s, Lq, kn, m, a0, a1);
                 a0 = fold_pm(a0, m);
                 a1 = fold_pm(a1, m);
                 if constexpr (EACH) {
@@ -329,27 +323,13 @@ int rotate(const fhe_rotsum_plan *p, const u64 *ct, u64 stride, u64 *out, u64 ou
     return FHE_OK;
 }
 
-// the checks both calls share, in the order include/fhe_hip.h lists them
+// the call check (rotsum_host.h) of both entry points; `each`: fhe_rotate_each_sp
 int check_call(const fhe_rotsum_plan *p, const void *ct, u64 stride, const void *out, u64 out_stride, u64 tap_stride, u64 count, const void *scratch,
                size_t scratch_bytes, bool each) {
     const fhe_ctx *c = p->ctx;
-    const u64 Ln = (u64)(c->k - 1) * c->n;
-    if (stride < 2 * Ln) return fail(FHE_ERR_PARAM, "ciphertext stride smaller than a size-2 ciphertext of %u primes", c->k - 1);
-    if (out_stride < 2 * Ln) return fail(FHE_ERR_PARAM, "output stride smaller than a size-2 ciphertext of %u primes", c->k - 1);
-    if (!count) return FHE_OK;
-    if (count * p->taps * 2 * c->k > 0x7fffffffULL) return fail(FHE_ERR_PARAM, "too many ciphertexts for one call");
-    const u64 out_batch = (count - 1) * out_stride + 2 * Ln;
-    if (each && tap_stride < out_batch) return fail(FHE_ERR_PARAM, "tap stride smaller than one batch of outputs");
-    const size_t need = scratch_words(p, count, each) * sizeof(u64);
-    if (!scratch || scratch_bytes < need) return fail(FHE_ERR_PARAM, "scratch too small");
-    const u64 in_words = (count - 1) * stride + 2 * Ln, out_words = each ? (p->taps - 1) * tap_stride + out_batch : out_batch;
-    if (each) {
-        if (overlap(ct, in_words, out, out_words)) return fail(FHE_ERR_PARAM, "output range overlaps the input range (fhe_rotate_each_sp has no in-place form)");
-    } else if (!(out == ct && out_stride == stride) && overlap(ct, in_words, out, out_words)) {
-        return fail(FHE_ERR_PARAM, "output range overlaps the input range (only out2 == ct2 with out_stride == stride may alias)");
-    }
-    if (overlap(scratch, need / 8, ct, in_words) || overlap(scratch, need / 8, out, out_words)) return fail(FHE_ERR_PARAM, "scratch overlaps the input or the output");
-    return FHE_OK;
+    const std::string why = rotsum::check_call(c->k, c->n, ct, stride, out, out_stride, count, count * p->taps * 2 * c->k, scratch_words(p, count, each) * sizeof(u64),
+                                               scratch, scratch_bytes, each ? p->taps : 0, tap_stride);
+    return why.empty() ? FHE_OK : fail(FHE_ERR_PARAM, "%s", why.c_str());
 }
 
 }  // namespace
@@ -362,24 +342,14 @@ extern "C" int fhe_rotsum_plan_create(const fhe_ctx *c, uint32_t taps, const uin
     if (weights) std::copy(weights, weights + w.size(), w.begin());
     const std::string why = rotsum::check_taps(n, c->t, k, taps, elts, w.data(), (const void *const *)d_keys);
     if (!why.empty()) return fail(FHE_ERR_PARAM, "%s", why.c_str());
-    // the context's own forward transform of X: slot s holds psi_r^(e_s)
-    std::vector<uint64_t> x((size_t)k * n, 0);
-    for (u32 r = 0; r < k; r++) x[(size_t)r * n + 1] = 1;
+    // the context's own forward transform of X, in a buffer of its own
     u64 *d_x = nullptr;
-    HIP_TRY(hipMalloc(&d_x, x.size() * 8));
-    int rc = FHE_OK;
-    if (hipMemcpy(d_x, x.data(), x.size() * 8, hipMemcpyHostToDevice) != hipSuccess) rc = fail(FHE_ERR_HIP, "upload of X");
-    if (!rc) rc = fhe_qbase_ntt(false, c, d_x, d_x, 1, nullptr);
-    if (!rc && (hipStreamSynchronize(nullptr) != hipSuccess || hipMemcpy(x.data(), d_x, x.size() * 8, hipMemcpyDeviceToHost) != hipSuccess))
-        rc = fail(FHE_ERR_HIP, "transform of X");
+    HIP_TRY(hipMalloc(&d_x, (size_t)k * n * 8));
+    std::vector<u32> f;
+    int rc = fhe_rot_slot_exponents(c, d_x, 0, "X", f);
     (void)hipFree(d_x);
     if (rc) return rc;
-    std::vector<u32> f, fr;
-    if (!rotsum::slot_exponents(x.data(), n, c->qb.primes[0], f)) return fail(FHE_ERR_PARAM, "the context's transform of X is not a set of odd powers of one root");
-    for (u32 r = 1; r < k; r++)
-        if (!rotsum::slot_exponents(x.data() + (size_t)r * n, n, c->qb.primes[r], fr) || fr != f)
-            return fail(FHE_ERR_PARAM, "the context's transforms order their slots differently from prime to prime");
-    fhe_rotsum_plan *p = new fhe_rotsum_plan;
+    std::unique_ptr<fhe_rotsum_plan> p(new fhe_rotsum_plan);
     p->ctx = c;
     p->taps = taps;
     p->elts.assign(elts, elts + taps);
@@ -390,13 +360,9 @@ extern "C" int fhe_rotsum_plan_create(const fhe_ctx *c, uint32_t taps, const uin
         p->ginv.push_back((u32)hostmath::powmod(g, n / 2 - 1, 2 * (u64)n));      // the units modulo 2n have exponent n / 2
         if (g == 1) p->id = (int)j;
         else p->rotations++;
-        if (!rotsum::slot_perm(f, g, perm.data() + (size_t)j * n)) {
-            delete p;
-            return fail(FHE_ERR_PARAM, "no slot permutation for Galois element %u", g);
-        }
         for (u32 r = 0; r < k; r++) wr[(size_t)j * k + r] = rotsum::weight_residue(w[j], c->t, c->qb.primes[r]);
-        keys[j] = g == 1 ? 0 : (u64)(uintptr_t)d_keys[j];
     }
+    if ((rc = fhe_rot_perm_keys(f, taps, elts, d_keys, perm.data(), keys.data()))) return rc;
     const size_t b_perm = perm.size() * 4, b_ginv = ((size_t)taps * 4 + 7) & ~(size_t)7, b_w = wr.size() * 8, b_keys = (size_t)taps * 8;
     std::vector<unsigned char> blob(b_perm + b_ginv + 2 * b_w + b_keys);
     std::vector<u64> ones(wr.size(), 1);
@@ -406,27 +372,21 @@ extern "C" int fhe_rotsum_plan_create(const fhe_ctx *c, uint32_t taps, const uin
     memcpy(blob.data() + b_perm + b_ginv + b_w, ones.data(), b_w);
     memcpy(blob.data() + b_perm + b_ginv + 2 * b_w, keys.data(), b_keys);
     if (hipMalloc(&p->d_block, blob.size()) != hipSuccess) {
-        delete p;
+        p->d_block = nullptr;
         return fail(FHE_ERR_NOMEM, "device allocation of %zu bytes for the rotate-sum plan", blob.size());
     }
-    if (hipMemcpy(p->d_block, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(p->d_block);
-        delete p;
-        return fail(FHE_ERR_HIP, "upload of the rotate-sum plan");
-    }
+    if (hipMemcpy(p->d_block, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(FHE_ERR_HIP, "upload of the rotate-sum plan");
     unsigned char *d = (unsigned char *)p->d_block;
     p->d_perm = (u32 *)d;
     p->d_ginv = (u32 *)(d + b_perm);
     p->d_w = (u64 *)(d + b_perm + b_ginv);
     p->d_w1 = (u64 *)(d + b_perm + b_ginv + b_w);
     p->d_keys = (const u64 **)(d + b_perm + b_ginv + 2 * b_w);
-    *out = p;
+    *out = p.release();
     return FHE_OK;
 }
 
 extern "C" int fhe_rotsum_plan_destroy(fhe_rotsum_plan *p) {
-    if (!p) return FHE_OK;
-    if (p->d_block) (void)hipFree(p->d_block);
     delete p;
     return FHE_OK;
 }

@@ -1,6 +1,6 @@
 // rotsum_host.h -- the host arithmetic of a rotate-sum plan (rotsum.hip, include/fhe_hip.h fhe_rotsum_plan_create): the checks on the taps
-// and the slot permutations pi_g, from a given transform of the monomial X.  No device, no HIP header: tools/rotsum_host_check.cpp builds
-// it alone, under the host sanitizers.
+// and the slot permutations pi_g, from a given transform of the monomial X; and the check on the operands of a call that rotsum.hip,
+// rotdiag.hip and rotbsgs.hip share.  No device, no HIP header: tools/rotsum_host_check.cpp builds it alone, under the host sanitizers.
 #pragma once
 #include <stdint.h>
 
@@ -82,6 +82,35 @@ inline bool slot_perm(const std::vector<uint32_t> &f, uint32_t g, uint32_t *perm
         perm[s] = src;
     }
     return true;
+}
+
+// do [a, a + a_words) and [b, b + b_words) share a 64-bit word (internal.h's overlap, for a header without the device's)
+inline bool overlap(const void *a, uint64_t a_words, const void *b, uint64_t b_words) {
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + a_words * 8, b0 = (uintptr_t)b, b1 = b0 + b_words * 8;
+    return a0 < b1 && b0 < a1;
+}
+
+// "" when fhe_rotate_sum_sp, fhe_rotate_each_sp, fhe_rotate_diag_sum_sp or fhe_rotate_bsgs_sp may run on these operands, otherwise the
+// reason, in the order include/fhe_hip.h lists the checks.  Nothing is dereferenced.  launch: the family's largest launch-size product;
+// need: the bytes of scratch the call takes; taps != 0: fhe_rotate_each_sp, out [taps] batches tap_stride words apart and no in-place form
+inline std::string check_call(uint32_t k, uint32_t n, const void *ct, uint64_t stride, const void *out, uint64_t out_stride, uint64_t count, uint64_t launch,
+                              size_t need, const void *scratch, size_t scratch_bytes, uint32_t taps = 0, uint64_t tap_stride = 0) {
+    const uint64_t Ln = (uint64_t)(k - 1) * n;
+    if (stride < 2 * Ln) return "ciphertext stride smaller than a size-2 ciphertext of " + std::to_string(k - 1) + " primes";
+    if (out_stride < 2 * Ln) return "output stride smaller than a size-2 ciphertext of " + std::to_string(k - 1) + " primes";
+    if (!count) return "";
+    if (launch > 0x7fffffffULL) return "too many ciphertexts for one call";
+    const uint64_t out_batch = (count - 1) * out_stride + 2 * Ln;
+    if (taps && tap_stride < out_batch) return "tap stride smaller than one batch of outputs";
+    if (!scratch || scratch_bytes < need) return "scratch too small";
+    const uint64_t in_words = (count - 1) * stride + 2 * Ln, out_words = taps ? (taps - 1) * tap_stride + out_batch : out_batch;
+    if (taps) {
+        if (overlap(ct, in_words, out, out_words)) return "output range overlaps the input range (fhe_rotate_each_sp has no in-place form)";
+    } else if (!(out == ct && out_stride == stride) && overlap(ct, in_words, out, out_words)) {
+        return "output range overlaps the input range (only out2 == ct2 with out_stride == stride may alias)";
+    }
+    if (overlap(scratch, need / 8, ct, in_words) || overlap(scratch, need / 8, out, out_words)) return "scratch overlaps the input or the output";
+    return "";
 }
 
 }  // namespace rotsum

@@ -398,7 +398,76 @@ class PlaneMapPlan:
             self.h = None
 
 
-class RotSumPlan:
+class _RotPlan:
+    """What RotSumPlan, RotDiagPlan and RotBsgsPlan share: the checks on the keys and on a list of Galois elements, the key tensors behind
+    the bare pointers the library holds, and the plan handle's life.  _STEM: fhe_<_STEM>_plan_create / _scratch_bytes / _plan_destroy."""
+
+    _STEM = None
+
+    def _open(self, ctx_level, keys):
+        from .keys import SpecialGaloisKeys                # keys.py imports this module
+        if not isinstance(keys, SpecialGaloisKeys):
+            raise ValueError("%s: SpecialGaloisKeys expected (KeyGenerator.generate_special_galois_keys), got %s" % (type(self).__name__, type(keys).__name__))
+        self.ctx, self.parent = ctx_level, keys.ctx
+
+    def _elements(self, vals, steps, limit, what=None):
+        """the Galois elements of one list, counted; what: "baby" / "giant", or None for the taps of a sum"""
+        from .keys import galois_element
+        elts = [galois_element(int(self.ctx.n), int(v)) if steps else int(v) for v in vals]
+        if not 1 <= len(elts) <= limit:
+            raise ValueError("%s: %d %s (1 .. %d)" % (type(self).__name__, len(elts), "taps" if what is None else what + " steps", limit))
+        return elts
+
+    def _check_elements(self, elts, what=None, tap=None):
+        """every element odd, in range and not repeated; tap(j): the family's own check of tap j, after the element's"""
+        who, n = type(self).__name__, int(self.ctx.n)
+        word = "" if what is None else what + " "
+        for j, g in enumerate(elts):
+            if not (g & 1) or not 0 < g < 2 * n:
+                raise ValueError("%s: %sGalois element %d must be odd and in [1, 2n = %d)" % (who, word, g, 2 * n))
+            if g in elts[:j]:
+                raise ValueError("%s: %sGalois element %d is repeated" % (who, word, g))
+            if tap is not None:
+                tap(j)
+
+    def _key_tensors(self, keys, elts):
+        """the key tensor of every element (None for 1), under the checks apply_galois makes before a bare pointer is handed over"""
+        who, row = type(self).__name__, []
+        for g in elts:
+            if g == 1:
+                row.append(None)
+                continue
+            if not keys.has(g):
+                raise ValueError("%s: no special Galois key for element %d (have %r); the fused call takes no hops" % (who, g, keys.elements()))
+            key = keys.key(g)
+            check_special_keys(self.ctx, keys.ctx, key, 1, who)
+            row.append(key)
+        return row
+
+    @staticmethod
+    def _key_pointers(row):
+        return (C.c_void_p * len(row))(*[None if k is None else k.data_ptr() for k in row])
+
+    def _create(self, *args):
+        h = C.c_void_p()
+        torch.cuda.synchronize(self.ctx.device)                              # the keys are complete before the plan's own (null-stream) transforms
+        _lib.call("fhe_%s_plan_create" % self._STEM, self.parent.h, *args, C.byref(h))
+        self.h = h
+
+    def scratch_bytes(self, count):
+        return int(getattr(_lib.load(), "fhe_%s_scratch_bytes" % self._STEM)(self.h, int(count)))
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h:
+            try:
+                getattr(_lib.load(), "fhe_%s_plan_destroy" % self._STEM)(h)
+            except Exception:
+                pass
+            self.h = None
+
+
+class RotSumPlan(_RotPlan):
     """The taps of Evaluator.rotate_sum / rotate_each (fhe_rotsum_plan_create: hoisted special-prime rotations of ONE ciphertext).
     ctx_level: the context the ciphertexts live in, the first k - 1 primes of keys.ctx; keys: SpecialGaloisKeys that hold every element
     directly (no hops); elements_or_steps: Galois elements (odd, pairwise distinct, 1 = the ciphertext itself, needs no key), or with
@@ -406,60 +475,32 @@ class RotSumPlan:
     alive: the library holds their device pointers."""
 
     MAX_TAPS = 64
+    _STEM = "rotsum"
 
     def __init__(self, ctx_level, special_galois_keys, elements_or_steps, weights=None, steps=False):
-        from .keys import SpecialGaloisKeys, galois_element                # keys.py imports this module
         keys = special_galois_keys
-        if not isinstance(keys, SpecialGaloisKeys):
-            raise ValueError("RotSumPlan: SpecialGaloisKeys expected (KeyGenerator.generate_special_galois_keys), got %s" % type(keys).__name__)
-        n, t = int(ctx_level.n), int(ctx_level.t)
-        elts = [galois_element(n, int(v)) if steps else int(v) for v in elements_or_steps]
+        self._open(ctx_level, keys)
+        t = int(ctx_level.t)
+        elts = self._elements(elements_or_steps, steps, self.MAX_TAPS)
         w = [1] * len(elts) if weights is None else [int(v) for v in np.asarray(weights).reshape(-1)]
-        if not 1 <= len(elts) <= self.MAX_TAPS:
-            raise ValueError("RotSumPlan: %d taps (1 .. %d)" % (len(elts), self.MAX_TAPS))
         if len(w) != len(elts):
             raise ValueError("RotSumPlan: %d weights for %d taps" % (len(w), len(elts)))
-        for j, g in enumerate(elts):
-            if not (g & 1) or not 0 < g < 2 * n:
-                raise ValueError("RotSumPlan: Galois element %d must be odd and in [1, 2n = %d)" % (g, 2 * n))
-            if g in elts[:j]:
-                raise ValueError("RotSumPlan: Galois element %d is repeated" % g)
+
+        def weight(j):
             if w[j] % t == 0:
                 raise ValueError("RotSumPlan: the weight of tap %d is 0 modulo t" % j)
-        self._keys = []
-        for g in elts:
-            if g == 1:
-                self._keys.append(None)
-                continue
-            if not keys.has(g):
-                raise ValueError("RotSumPlan: no special Galois key for element %d (have %r); the fused call takes no hops" % (g, keys.elements()))
-            key = keys.key(g)
-            check_special_keys(ctx_level, keys.ctx, key, 1, "RotSumPlan")    # the checks apply_galois makes before a bare pointer is handed over
-            self._keys.append(key)
-        self.ctx, self.parent, self.elements = ctx_level, keys.ctx, elts
-        self.weights = [v % t for v in w]
+        self._check_elements(elts, tap=weight)
+        self._keys = self._key_tensors(keys, elts)
+        self.elements, self.weights = elts, [v % t for v in w]
         e = np.array(elts, dtype=np.uint32)
         wv = np.array(self.weights, dtype=np.uint64)
-        kp = (C.c_void_p * len(elts))(*[None if k is None else k.data_ptr() for k in self._keys])
-        h = C.c_void_p()
-        torch.cuda.synchronize(ctx_level.device)                             # the keys are complete before the plan's own (null-stream) transform of X
-        _lib.call("fhe_rotsum_plan_create", keys.ctx.h, len(elts), e.ctypes.data_as(C.c_void_p), wv.ctypes.data_as(C.c_void_p), kp, C.byref(h))
-        self.h = h
+        self._create(len(elts), e.ctypes.data_as(C.c_void_p), wv.ctypes.data_as(C.c_void_p), self._key_pointers(self._keys))
 
     def scratch_bytes(self, count, each=False):
         return int(_lib.load().fhe_rotsum_scratch_bytes(self.h, int(count), int(bool(each))))
 
-    def __del__(self):
-        h = getattr(self, "h", None)
-        if h:
-            try:
-                _lib.load().fhe_rotsum_plan_destroy(h)
-            except Exception:
-                pass
-            self.h = None
 
-
-class RotDiagPlan:
+class RotDiagPlan(_RotPlan):
     """The taps of Evaluator.rotate_diag_sum (fhe_rotdiag_plan_create: a diagonal linear map on the slots of ONE ciphertext under one
     special-prime key switch): out = sum_j d_j (.) rot_j(x) slot by slot.  ctx_level, special_galois_keys, elements_or_steps and steps are
     RotSumPlan's; diagonals: [G][n] slot values modulo t in flat row order (row 0 then row 1), none of them all zero -- they go through
@@ -467,61 +508,31 @@ class RotDiagPlan:
     device pointers."""
 
     MAX_TAPS = 64
+    _STEM = "rotdiag"
 
     def __init__(self, ctx_level, special_galois_keys, elements_or_steps, diagonals, steps=False):
         from .client import BatchEncoder
-        from .keys import SpecialGaloisKeys, galois_element                # keys.py imports this module
         keys = special_galois_keys
-        if not isinstance(keys, SpecialGaloisKeys):
-            raise ValueError("RotDiagPlan: SpecialGaloisKeys expected (KeyGenerator.generate_special_galois_keys), got %s" % type(keys).__name__)
+        self._open(ctx_level, keys)
         n, t = int(ctx_level.n), int(ctx_level.t)
-        elts = [galois_element(n, int(v)) if steps else int(v) for v in elements_or_steps]
-        if not 1 <= len(elts) <= self.MAX_TAPS:
-            raise ValueError("RotDiagPlan: %d taps (1 .. %d)" % (len(elts), self.MAX_TAPS))
+        elts = self._elements(elements_or_steps, steps, self.MAX_TAPS)
         d = np.asarray(diagonals)
         if d.ndim != 2 or d.shape != (len(elts), n):
             raise ValueError("RotDiagPlan: diagonals of shape %r for %d taps of %d slots" % (tuple(d.shape), len(elts), n))
         d = np.array([[int(v) % t for v in row] for row in d], dtype=np.uint64)
-        for j, g in enumerate(elts):
-            if not (g & 1) or not 0 < g < 2 * n:
-                raise ValueError("RotDiagPlan: Galois element %d must be odd and in [1, 2n = %d)" % (g, 2 * n))
-            if g in elts[:j]:
-                raise ValueError("RotDiagPlan: Galois element %d is repeated" % g)
+
+        def diagonal(j):
             if not d[j].any():
                 raise ValueError("RotDiagPlan: the diagonal of tap %d is 0 modulo t in every slot" % j)
-        self._keys = []
-        for g in elts:
-            if g == 1:
-                self._keys.append(None)
-                continue
-            if not keys.has(g):
-                raise ValueError("RotDiagPlan: no special Galois key for element %d (have %r); the fused call takes no hops" % (g, keys.elements()))
-            key = keys.key(g)
-            check_special_keys(ctx_level, keys.ctx, key, 1, "RotDiagPlan")   # the checks apply_galois makes before a bare pointer is handed over
-            self._keys.append(key)
-        self.ctx, self.parent, self.elements = ctx_level, keys.ctx, elts
+        self._check_elements(elts, tap=diagonal)
+        self._keys = self._key_tensors(keys, elts)
+        self.elements = elts
         self.plains = np.ascontiguousarray(BatchEncoder(ctx_level).encode_host(d), dtype=np.uint64)      # [G][n] coefficients modulo t
         e = np.array(elts, dtype=np.uint32)
-        kp = (C.c_void_p * len(elts))(*[None if k is None else k.data_ptr() for k in self._keys])
-        h = C.c_void_p()
-        torch.cuda.synchronize(ctx_level.device)                             # the keys are complete before the plan's own (null-stream) transforms
-        _lib.call("fhe_rotdiag_plan_create", keys.ctx.h, len(elts), e.ctypes.data_as(C.c_void_p), self.plains.ctypes.data_as(C.c_void_p), kp, C.byref(h))
-        self.h = h
-
-    def scratch_bytes(self, count):
-        return int(_lib.load().fhe_rotdiag_scratch_bytes(self.h, int(count)))
-
-    def __del__(self):
-        h = getattr(self, "h", None)
-        if h:
-            try:
-                _lib.load().fhe_rotdiag_plan_destroy(h)
-            except Exception:
-                pass
-            self.h = None
+        self._create(len(elts), e.ctypes.data_as(C.c_void_p), self.plains.ctypes.data_as(C.c_void_p), self._key_pointers(self._keys))
 
 
-class RotBsgsPlan:
+class RotBsgsPlan(_RotPlan):
     """The plan of Evaluator.rotate_bsgs (fhe_rotbsgs_plan_create: a baby-step / giant-step linear map on the slots of ONE ciphertext):
     out = sum_i rot_(h_i)( sum_j d_(i,j) (.) rot_(g_j)(x) ) slot by slot, G1 G2 diagonals under G1 + G2 keys.  ctx_level,
     special_galois_keys and steps are RotSumPlan's; baby / giant: the two lists of Galois elements (or row rotations LEFT with steps=True),
@@ -530,26 +541,17 @@ class RotBsgsPlan:
     diagonals of a map.  The plan keeps the key tensors alive: the library holds their device pointers."""
 
     MAX_STEPS = 64
+    _STEM = "rotbsgs"
 
     def __init__(self, ctx_level, special_galois_keys, baby, giant, diagonals, steps=False):
         from .client import BatchEncoder
-        from .keys import SpecialGaloisKeys, galois_element                # keys.py imports this module
         keys = special_galois_keys
-        if not isinstance(keys, SpecialGaloisKeys):
-            raise ValueError("RotBsgsPlan: SpecialGaloisKeys expected (KeyGenerator.generate_special_galois_keys), got %s" % type(keys).__name__)
+        self._open(ctx_level, keys)
         n, t = int(ctx_level.n), int(ctx_level.t)
-        lists = []
-        for what, vals in (("baby", baby), ("giant", giant)):
-            elts = [galois_element(n, int(v)) if steps else int(v) for v in vals]
-            if not 1 <= len(elts) <= self.MAX_STEPS:
-                raise ValueError("RotBsgsPlan: %d %s steps (1 .. %d)" % (len(elts), what, self.MAX_STEPS))
-            for j, g in enumerate(elts):
-                if not (g & 1) or not 0 < g < 2 * n:
-                    raise ValueError("RotBsgsPlan: %s Galois element %d must be odd and in [1, 2n = %d)" % (what, g, 2 * n))
-                if g in elts[:j]:
-                    raise ValueError("RotBsgsPlan: %s Galois element %d is repeated" % (what, g))
-            lists.append(elts)
-        b, g = lists
+        b = self._elements(baby, steps, self.MAX_STEPS, "baby")
+        self._check_elements(b, "baby")
+        g = self._elements(giant, steps, self.MAX_STEPS, "giant")
+        self._check_elements(g, "giant")
         d = np.asarray(diagonals)
         if d.ndim != 3 or d.shape != (len(g), len(b), n):
             raise ValueError("RotBsgsPlan: diagonals of shape %r for %d giant and %d baby steps of %d slots" % (tuple(d.shape), len(g), len(b), n))
@@ -566,42 +568,13 @@ class RotBsgsPlan:
         for j in range(len(b)):
             if not present[:, j].any():
                 raise ValueError("RotBsgsPlan: baby step %d has no present pair (every diagonal of its column is 0 modulo t)" % j)
-        self._keys = []
-        for elts in lists:
-            row = []
-            for e in elts:
-                if e == 1:
-                    row.append(None)
-                    continue
-                if not keys.has(e):
-                    raise ValueError("RotBsgsPlan: no special Galois key for element %d (have %r); the fused call takes no hops" % (e, keys.elements()))
-                key = keys.key(e)
-                check_special_keys(ctx_level, keys.ctx, key, 1, "RotBsgsPlan")   # the checks apply_galois makes before a bare pointer is handed over
-                row.append(key)
-            self._keys.append(row)
-        self.ctx, self.parent, self.baby, self.giant = ctx_level, keys.ctx, b, g
+        self._keys = [self._key_tensors(keys, b), self._key_tensors(keys, g)]
+        self.baby, self.giant = b, g
         enc = BatchEncoder(ctx_level).encode_host(d.reshape(len(g) * len(b), n))
         self.plains = np.ascontiguousarray(np.asarray(enc, dtype=np.uint64).reshape(len(g), len(b), n))      # [G2][G1][n] coefficients modulo t
         eb, eg = np.array(b, dtype=np.uint32), np.array(g, dtype=np.uint32)
-        kb = (C.c_void_p * len(b))(*[None if k is None else k.data_ptr() for k in self._keys[0]])
-        kg = (C.c_void_p * len(g))(*[None if k is None else k.data_ptr() for k in self._keys[1]])
-        h = C.c_void_p()
-        torch.cuda.synchronize(ctx_level.device)                             # the keys are complete before the plan's own (null-stream) transforms
-        _lib.call("fhe_rotbsgs_plan_create", keys.ctx.h, len(b), eb.ctypes.data_as(C.c_void_p), len(g), eg.ctypes.data_as(C.c_void_p),
-                  self.plains.ctypes.data_as(C.c_void_p), kb, kg, C.byref(h))
-        self.h = h
-
-    def scratch_bytes(self, count):
-        return int(_lib.load().fhe_rotbsgs_scratch_bytes(self.h, int(count)))
-
-    def __del__(self):
-        h = getattr(self, "h", None)
-        if h:
-            try:
-                _lib.load().fhe_rotbsgs_plan_destroy(h)
-            except Exception:
-                pass
-            self.h = None
+        self._create(len(b), eb.ctypes.data_as(C.c_void_p), len(g), eg.ctypes.data_as(C.c_void_p), self.plains.ctypes.data_as(C.c_void_p),
+                     self._key_pointers(self._keys[0]), self._key_pointers(self._keys[1]))
 
 
 def check_evaluation_keys(ctx, evk_ntt, dbc, need, who):
@@ -893,49 +866,37 @@ class Evaluator:
             raise ValueError("%s: ciphertexts of size 2 of this context only, got %r" % (who, tuple(a.shape)))
         return self._npolys(a) // 2
 
+    def _rotate_fused(self, a, plan, who, kind, entry, out):
+        """rotate_sum, rotate_diag_sum and rotate_bsgs: one ciphertext batch in, one out (possibly in place), under one plan"""
+        count = self._rotsum_operand(a, plan, who, kind)
+        if out is not None and (tuple(out.shape) != tuple(a.shape) or out.dtype != a.dtype or not out.is_contiguous() or out.device != a.device):
+            raise ValueError("%s: `out` must be a contiguous int64 tensor of shape %r on the input's device" % (who, tuple(a.shape)))
+        out = torch.empty_like(a) if out is None else out
+        ctw = 2 * self.ctx.k * self.ctx.n
+        nbytes = plan.scratch_bytes(count)
+        scr = self._scratch_buf(nbytes)
+        _lib.call(entry, plan.h, _ptr(a), ctw, _ptr(out), ctw, count, _ptr(scr), nbytes, _stream())
+        return out
+
     def rotate_sum(self, a, plan, out=None):
         """sum over the plan's taps of w_j * sigma_(g_j)(a), key-switched back to s ONCE (fhe_rotate_sum_sp): one set of forward transforms,
         one accumulation over all taps, one set of inverse transforms and one rounding, whatever the number of taps.  Decrypts to what
         the composition of apply_galois, multiply_plain by the constant w_j and add decrypts to; the ciphertext bits are its own.
         `out` may be `a` itself (in place) or a contiguous tensor of the same shape that does not overlap it."""
-        count = self._rotsum_operand(a, plan, "rotate_sum")
-        if out is not None and (tuple(out.shape) != tuple(a.shape) or out.dtype != a.dtype or not out.is_contiguous() or out.device != a.device):
-            raise ValueError("rotate_sum: `out` must be a contiguous int64 tensor of shape %r on the input's device" % (tuple(a.shape),))
-        out = torch.empty_like(a) if out is None else out
-        ctw = 2 * self.ctx.k * self.ctx.n
-        nbytes = plan.scratch_bytes(count)
-        scr = self._scratch_buf(nbytes)
-        _lib.call("fhe_rotate_sum_sp", plan.h, _ptr(a), ctw, _ptr(out), ctw, count, _ptr(scr), nbytes, _stream())
-        return out
+        return self._rotate_fused(a, plan, "rotate_sum", RotSumPlan, "fhe_rotate_sum_sp", out)
 
     def rotate_diag_sum(self, a, plan, out=None):
         """sum over the plan's taps of d_j (.) rot_j(a) slot by slot, key-switched back to s ONCE (fhe_rotate_diag_sum_sp): rotate_sum with
         a vector of slot values per tap where it has one integer -- the diagonal method for a matrix applied to the slot vector, a filter
         that is right at the tile border, a masked move of slots.  Decrypts to what the composition of apply_galois, multiply_plain by the
         encoded diagonal and add decrypts to; the ciphertext bits are its own.  `out` as for rotate_sum."""
-        count = self._rotsum_operand(a, plan, "rotate_diag_sum", RotDiagPlan)
-        if out is not None and (tuple(out.shape) != tuple(a.shape) or out.dtype != a.dtype or not out.is_contiguous() or out.device != a.device):
-            raise ValueError("rotate_diag_sum: `out` must be a contiguous int64 tensor of shape %r on the input's device" % (tuple(a.shape),))
-        out = torch.empty_like(a) if out is None else out
-        ctw = 2 * self.ctx.k * self.ctx.n
-        nbytes = plan.scratch_bytes(count)
-        scr = self._scratch_buf(nbytes)
-        _lib.call("fhe_rotate_diag_sum_sp", plan.h, _ptr(a), ctw, _ptr(out), ctw, count, _ptr(scr), nbytes, _stream())
-        return out
+        return self._rotate_fused(a, plan, "rotate_diag_sum", RotDiagPlan, "fhe_rotate_diag_sum_sp", out)
 
     def rotate_bsgs(self, a, plan, out=None):
         """sum_i rot_(h_i)( sum_j d_(i,j) (.) rot_(g_j)(a) ) slot by slot (fhe_rotate_bsgs_sp): the baby-step / giant-step form of
         rotate_diag_sum, G1 + G2 keys for G1 G2 diagonals; c_0 is rounded once.  Decrypts to what the composition of rotate_each,
         multiply_plain, add and apply_galois decrypts to; the ciphertext bits are its own.  `out` as for rotate_sum."""
-        count = self._rotsum_operand(a, plan, "rotate_bsgs", RotBsgsPlan)
-        if out is not None and (tuple(out.shape) != tuple(a.shape) or out.dtype != a.dtype or not out.is_contiguous() or out.device != a.device):
-            raise ValueError("rotate_bsgs: `out` must be a contiguous int64 tensor of shape %r on the input's device" % (tuple(a.shape),))
-        out = torch.empty_like(a) if out is None else out
-        ctw = 2 * self.ctx.k * self.ctx.n
-        nbytes = plan.scratch_bytes(count)
-        scr = self._scratch_buf(nbytes)
-        _lib.call("fhe_rotate_bsgs_sp", plan.h, _ptr(a), ctw, _ptr(out), ctw, count, _ptr(scr), nbytes, _stream())
-        return out
+        return self._rotate_fused(a, plan, "rotate_bsgs", RotBsgsPlan, "fhe_rotate_bsgs_sp", out)
 
     def rotate_each(self, a, plan):
         """[taps] + a.shape: sigma_(g_j)(a) key-switched back to s for every tap of the plan, the forward transforms shared

@@ -1,4 +1,4 @@
-// rotsum_host_check.cpp -- the host arithmetic of a rotate-sum plan (csrc/rotsum_host.h: the checks on the taps, the slot permutations
+// rotsum_host_check.cpp -- the host arithmetic of a rotate-sum plan (csrc/rotsum_host.h: the checks on the taps and on a call, the slot permutations
 // from a transform of X, the weights' residues) in a program of its own, for a CPU build under the host sanitizers:
 //     c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/rotsum_host_check.cpp -o rotsum_host_check
 // No device, no library.  It builds the transform of X itself, in two slot orders, and compares every permutation with the definition:
@@ -138,6 +138,62 @@ int main() {
         std::vector<uint64_t> w(64, 1);
         for (uint32_t j = 0; j < 64; j++) e[j] = 2 * j + 1;
         CHECK(rotsum::check_taps(n, t, 2, 64, e.data(), w.data(), nullptr).empty());
+    }
+    // the call check of the four rotation entry points: made-up addresses, nothing is dereferenced.  k = 3 primes of n = 1024: a size-2
+    // ciphertext is ctw = 4096 words; 2 ciphertexts in, 2 out, 1000 words (8000 bytes) of scratch
+    {
+        const uint32_t ck = 3;
+        const uint64_t ctw = 2 * (uint64_t)(ck - 1) * n, count = 2, launch = count * ck * ck;
+        const size_t need = 8000;
+        const auto at = [](uint64_t word) { return (const void *)(uintptr_t)(0x10000000ULL + 8 * word); };
+        const void *ct = at(0), *out = at(100000), *scr = at(200000);
+        const auto has = [](const std::string &why, const char *word) { return why.find(word) != std::string::npos; };
+        const auto sum = [&](const void *c, uint64_t stride, const void *o, uint64_t ostride, uint64_t cnt, uint64_t lnch, const void *s, size_t bytes) {
+            return rotsum::check_call(ck, n, c, stride, o, ostride, cnt, lnch, need, s, bytes);
+        };
+        const auto each = [&](const void *c, const void *o, uint64_t tap_stride, const void *s) {
+            return rotsum::check_call(ck, n, c, ctw, o, ctw, count, launch, need, s, need, 3, tap_stride);
+        };
+        CHECK(sum(ct, ctw, out, ctw, count, launch, scr, need).empty());
+        CHECK(sum(ct, ctw + 8, out, ctw + 24, count, launch, scr, need + 1).empty());                 // padded strides, a larger buffer
+        CHECK(each(ct, out, count * ctw, scr).empty());
+        // every refusal, one at a time, by the word the callers' tests look for
+        std::string why = sum(ct, ctw - 1, out, ctw, count, launch, scr, need);
+        CHECK(has(why, "ciphertext stride") && has(why, "of 2 primes"));
+        why = sum(ct, ctw, out, ctw - 1, count, launch, scr, need);
+        CHECK(has(why, "output stride") && has(why, "of 2 primes"));
+        CHECK(has(sum(ct, ctw, out, ctw, count, 0x80000000ULL, scr, need), "too many"));
+        CHECK(sum(ct, ctw, out, ctw, count, 0x7fffffffULL, scr, need).empty());
+        CHECK(has(each(ct, out, count * ctw - 1, scr), "tap stride"));
+        CHECK(has(sum(ct, ctw, out, ctw, count, launch, scr, need - 1), "scratch too small"));
+        CHECK(has(sum(ct, ctw, out, ctw, count, launch, nullptr, need), "scratch too small"));
+        why = sum(ct, ctw, at(2 * ctw - 1), ctw, count, launch, scr, need);                           // the last input word is the first output word
+        CHECK(has(why, "overlaps") && !has(why, "scratch overlaps") && has(why, "only out2 == ct2"));
+        CHECK(sum(ct, ctw, at(2 * ctw), ctw, count, launch, scr, need).empty());                      // adjacent ranges share no word
+        CHECK(has(sum(ct, ctw, out, ctw, count, launch, at(2 * ctw - 1), need), "scratch overlaps"));     // scratch on the input's last word
+        CHECK(has(sum(ct, ctw, out, ctw, count, launch, at(100000 - 1000 + 1), need), "scratch overlaps"));   // scratch's last word on the output's first
+        CHECK(sum(ct, ctw, out, ctw, count, launch, at(100000 - 1000), need).empty());
+        // the order of the refusals: strides, the launch size, the tap stride, scratch, the operands' overlap, scratch's overlap
+        CHECK(has(sum(ct, ctw - 1, out, ctw - 1, count, 0x80000000ULL, nullptr, 0), "ciphertext stride"));
+        CHECK(has(sum(ct, ctw, out, ctw - 1, count, 0x80000000ULL, nullptr, 0), "output stride"));
+        CHECK(has(sum(ct, ctw, ct, ctw + 8, count, 0x80000000ULL, nullptr, 0), "too many"));
+        CHECK(has(rotsum::check_call(ck, n, ct, ctw, ct, ctw, count, launch, need, nullptr, 0, 3, 1), "tap stride"));
+        CHECK(has(sum(ct, ctw, ct, ctw + 8, count, launch, nullptr, 0), "scratch too small"));
+        why = sum(ct, ctw, ct, ctw + 8, count, launch, ct, need);
+        CHECK(has(why, "overlaps") && !has(why, "scratch overlaps"));
+        // no ciphertext: clean after the strides, whatever the rest is
+        CHECK(sum(ct, ctw, ct, ctw + 8, 0, ~0ULL, nullptr, 0).empty());
+        CHECK(rotsum::check_call(ck, n, ct, ctw, ct, ctw, 0, ~0ULL, need, nullptr, 0, 3, 0).empty());
+        CHECK(has(sum(ct, ctw - 1, out, ctw, 0, launch, scr, need), "ciphertext stride"));
+        // in place: out == ct with equal strides for the sums, never for fhe_rotate_each_sp; the same pointer with another stride is refused
+        CHECK(sum(ct, ctw, ct, ctw, count, launch, scr, need).empty());
+        CHECK(sum(ct, ctw + 8, ct, ctw + 8, count, launch, scr, need).empty());
+        why = each(ct, ct, count * ctw, scr);
+        CHECK(has(why, "overlaps") && has(why, "no in-place form"));
+        why = sum(ct, ctw, ct, ctw + 8, count, launch, scr, need);
+        CHECK(has(why, "overlaps") && has(why, "only out2 == ct2"));
+        CHECK(each(at(3 * count * ctw), at(0), count * ctw, scr).empty());                            // the LAST tap's batch ends just before the input
+        CHECK(has(each(at(3 * count * ctw - 1), at(0), count * ctw, scr), "overlaps"));               // ... and on its first word
     }
     // centred lifts
     const uint64_t q = 0x3FFFFFFF000001ULL;
