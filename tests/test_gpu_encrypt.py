@@ -243,3 +243,54 @@ def test_decrypt_batch_equals_the_oracle_big_integer_decryption(fhe, oracle_mod,
     assert b == [0, 0, 0]
     check(ctx.random_ct(2, size=4, seed=78), "random size 4")
     assert dec.decrypt_batch(ctx.empty(0)).shape == (0, ctx.n)
+
+
+def _lift_contexts(fhe):
+    """(label, q, t, arithmetic of fhe_encrypt_batch): all at n = 1024 (every prime here is 1 modulo 2048).  The arithmetic follows from
+    the base as csrc/encrypt.hip chooses it: pseudo-Mersenne class 1 -> EncPmA, class 2 -> EncPmB, no class and primes of 34 .. 58 bits ->
+    EncShoup, 59 .. 61-bit primes -> the five launches only"""
+    import decrypt_craft as dc
+    from packed_oracle import T41
+    P = {name: fhe.PRESETS[name]["q"] for name in ("P4096", "SEAL23_4096", "P8192")}
+    return [("P4096", P["P4096"], 1 << 14, "EncShoup"), ("SEAL23_4096", P["SEAL23_4096"], 1 << 14, "EncPmA"), ("P8192", P["P8192"], 1 << 14, "EncPmA"),
+            ("Q4-k3-even", dc.primes("Q4", 3), 1 << 14, "EncPmA"), ("Q4-k3-odd", dc.primes("Q4", 3), 65537, "EncPmA"),
+            ("W58-T41", dc.primes("W58", 2), T41, "EncPmB"), ("W61", dc.primes("W61", 2), (1 << 59) + 1, "five launches")]
+
+
+@pytest.mark.parametrize("case", range(7), ids=["P4096", "SEAL23_4096", "P8192", "Q4-k3-even", "Q4-k3-odd", "W58-T41", "W61"])
+def test_plaintext_lift_at_the_threshold_and_at_wide_plain_moduli(fhe, oracle_mod, case):
+    """The lift of k_enc_finish and of all three k_enc_fused arithmetics (Delta m, + q mod t from thr = (t + 1) >> 1 upward) on the
+    coefficients 0, 1, thr - 2 .. thr + 1, t - 2, t - 1 -- the threshold coefficient itself, even t, odd t, t = T41 and t = 2^59 + 1 beside
+    61-bit primes (59..61-bit primes keep the five launches) --, a row of t - 1 and a row of thr: fused (two and four waves per SIMD) ==
+    five launches, == the oracle's keyed encryption bit for bit, decrypts to the rows exactly with the oracle's noise figure."""
+    label, q, t, arith = _lift_contexts(fhe)[case]
+    n = 1024
+    ctx, orc = fhe.SEALContext(n, q, t), oracle_mod.Oracle(n, q, t)
+    pm_class, bits = fhe._lib.call("fhe_arith_path", ctx.h) & 3, [p.bit_length() for p in q]      # what fhe_encrypt_batch dispatches on
+    assert pm_class == {"EncPmA": 1, "EncPmB": 2}.get(arith, 0), "%s: pseudo-Mersenne class %d, the test means %s" % (label, pm_class, arith)
+    assert arith != "EncShoup" or (max(bits) <= 58 and min(bits) >= 34)
+    assert arith != "five launches" or max(bits) > 58
+    kg = fhe.KeyGenerator(ctx, seed=17)
+    pk, sk = fhe.to_host(kg.public_key()), fhe.to_host(kg.secret_key())
+    thr = (t + 1) >> 1
+    vals = [0, 1, thr - 2, thr - 1, thr, thr + 1, t - 2, t - 1]
+    row = np.array(vals * (n // 8), dtype=np.uint64)
+    np.random.default_rng(23).shuffle(row)
+    plains = np.stack([row, np.full(n, t - 1, dtype=np.uint64), np.full(n, thr, dtype=np.uint64)])
+    first = (1 << 35) + 3
+    outs = []
+    for sw in ({}, {"FHE_ENC_OCC": 4}, {"FHE_ENC_UNFUSED": 1}):
+        c2 = fhe.SEALContext(n, q, t, switches=sw) if sw else ctx
+        der = fhe.DeviceEncryptor(c2, kg.public_key(), key=KEY, reproducible=True)
+        der.seek(first)
+        outs.append(der.encrypt_plains(fhe.to_device(plains, ctx.device)))
+    print("\n%s: ctx.k = %d, t = %d, pseudo-Mersenne class %d, prime bits %s: %s" % (label, ctx.k, t, pm_class, bits, arith))
+    assert torch.equal(outs[0], outs[2]) and torch.equal(outs[1], outs[2])
+    got = fhe.to_host(outs[0])
+    dec = fhe.Decryptor(ctx, kg.secret_key())
+    back, budgets = dec.decrypt_batch(outs[0], with_budget=True)
+    assert np.array_equal(back, plains)
+    for i in range(len(plains)):
+        assert np.array_equal(got[i], orc.encrypt_keyed(pk, plains[i], KEY, first + i)), (label, i)
+        want, nb, mb = orc.decrypt_noise_bits(sk, got[i])
+        assert np.array_equal(want, plains[i]) and budgets[i] == max(0, mb - nb - 1) and budgets[i] > 0, (label, i, budgets[i], nb, mb)
