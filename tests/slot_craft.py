@@ -5,7 +5,7 @@ Everything here is integer arithmetic modulo each prime; no floating point is in
 arrays shaped [..., k, n] (n slots in the CPU oracle's NTT order), centred values and sums of centred values are int64.
 A modular product of two residues is formed from limbs of 63 - bits(p) bits so that no intermediate leaves 64 bits, for
 primes of up to 57 bits (test_slot_craft_cpu.py checks it against Python integers up to 48 bits, test_dct_u64_craft_cpu.py
-up to 57).
+up to 57); from 58 to 61 bits the product runs on Python integers (jpeg_u64_craft.py's 58- and 61-bit bases).
 
 The model is slotwise, so the order in which the kernels hold the slots does not matter: a constant's slot value meets
 the data's value of the same slot in every order.
@@ -143,9 +143,9 @@ class SlotModel:
         self.Pi = self.P.astype(np.int64)
         self.H = (self.P - U(1)) // U(2)                            # (p - 1) / 2: the largest centred residue
         bits = max(p.bit_length() for p in self.q)
-        assert bits <= 57                                           # limbs of at least 6 bits (dct_u64_craft.py: the fused u64 pair's primes)
-        self.w = 63 - bits
-        self.limbs = -(-bits // self.w)
+        assert bits <= 61                                           # the library's own limit; above 57 bits mul() runs on Python integers
+        self.w = 63 - bits if bits <= 57 else 0                     # limbs of at least 6 bits (dct_u64_craft.py: the fused u64 pair's primes)
+        self.limbs = -(-bits // self.w) if self.w else 0
         self.inv2 = (self.P + U(1)) // U(2)
         self.C = np.stack([self.plain_slots(orc.encode(v)) for v in LINE_CONSTS])                # [12, k, n]
         e8 = self.plain_slots(orc.encode(0.125))
@@ -162,6 +162,8 @@ class SlotModel:
         return np.stack([self.orc.ntt_fwd(lift[i], i) for i in range(self.k)])
 
     def mul(self, a, b):
+        if not self.w:                                              # 58..61 bits (jpeg_u64_craft.py): no limb width leaves room in 64 bits
+            return (np.asarray(a).astype(object) * np.asarray(b).astype(object) % self.P.astype(object)).astype(U)
         mask, w, r = U((1 << self.w) - 1), U(self.w), None
         for i in reversed(range(self.limbs)):
             t = a * ((b >> U(self.w * i)) & mask)
