@@ -41,7 +41,11 @@ __device__ __forceinline__ u64 mul_shoup(u64 x, u64 w, u64 wp, u64 q) {
 //  * that chain's high word is kept demanded by and-ing it with a zero the compiler cannot see through
 //    (fhe_opaque_zero: a __device__ word that nobody writes; one scalar load per kernel);
 //  * the high word of x * wp leaves out the low x low partial product and the carries of the cross terms: qhat in
-//    [exact - 2, exact], so the result is x * w mod q + {0, 1, 2} q, i.e. in [0, 4q) for ANY 64-bit x.
+//    [exact - 2, exact], and the exact Shoup quotient is itself 0 or 1 below floor(x w / q) (1 only for x w mod q below
+//    x (w 2^64 mod q) / 2^64, i.e. rarely for a small x), so the result is x * w mod q + {0 .. 3} q, in [0, 4q) for ANY
+//    64-bit x.  With x < q a seeded search reaches the excess 2 and never 3; 3 needs all three at once: a large x, a residue w whose
+//    companion has a full high word (a negative scalar) and a wide prime.  x = 0x78b2b578c230fce6 (above 8q) times
+//    w = -474698375 modulo q = 0x3ffffffffff9001 returns 3q + (x w mod q) (tests/packed_craft.py).
 // 2 v_mul_hi_u32 + 7 v_mad_u64_u32: 4.5 against 3.5 products/clk/CU, 4.2 against 3.3 as a butterfly without the
 // conditional subtraction the wider range makes unnecessary (tools/ubench4.hip, profiles/r02_ubench4_shoup_products.txt;
 // the exact product written the same way measured no faster inside the transforms).
@@ -73,7 +77,8 @@ __device__ __forceinline__ u64 mul_shoup_lazy4_acc(u64 x, u64 w, u64 wp, u64 nq,
     const u32 hi = (u32)(P >> 32) + (u32)C + ((u32)(C >> 32) & zero);
     return ((u64)hi << 32) | (u32)P;
 }
-// any 64-bit v -> v mod q + {0, 1, 2} q, below 4q  (product with 1; one_p = floor(2^64 / q))
+// any 64-bit v -> v mod q + at most 3 q, below 4q  (product with 1; one_p = floor(2^64 / q)).  Observed for v < 32q: a multiple of
+// q comes back as exactly q; otherwise canonical on 54- to 58-bit primes, at most q too much on 36/37-bit ones (packed_arith.h, canon)
 __device__ __forceinline__ u64 reduce_lazy4(u64 v, u64 one_p, u64 nq, u32 zero) { return mul_shoup_lazy4(v, 1, one_p, nq, zero); }
 
 // a * b mod q for a, b in [0, q); Barrett with two multiplications, result in [0, q).

@@ -15,6 +15,11 @@ struct PkArith {
         if constexpr (LAZY) return mul_shoup_lazy4(x, w.x, w.y, nq, zero);
         else return mul_shoup(x, w.x, w.y, q);
     }
+    // [0, 4q) -> [0, q).  Behind post every interval up to the product's largest excess occurs.  Behind the product by 1 of a sum
+    // below 32q the subtraction is still needed: a sum that is a multiple of q comes back as exactly q (every j q, j = 1 .. 31, on
+    // every prime: whenever an output is 0), and on the 36/37-bit primes other sums come back in [q, 2q) too; on the 54- to 58-bit
+    // primes a seeded search of 2^18 sums per prime found the product by 1 canonical everywhere else (observed, not proved).
+    // DESIGN.md 3.12.1 has the table.
     __device__ __forceinline__ u64 canon(u64 x) const {
         if constexpr (LAZY) return csub(csub(x, 2 * q), q);
         else return x;
