@@ -152,6 +152,10 @@ SIGNATURES = {
     "fhe_encrypt_scratch_bytes": (_sz, [_vp, _u64]),
     "fhe_encrypt_batch": (_i, [_vp, _vp, _vp, _u64, C.c_char_p, _u64, _vp, _vp, _sz, _vp]),
     "fhe_encrypt_draws": (_i, [_vp, C.c_char_p, _u64, _u64, _vp, _vp]),
+    "fhe_expand_seeded": (_i, [_vp, _vp, _u64, C.c_char_p, _u64, _vp, _vp]),
+    "fhe_seed_expand_a": (_i, [_vp, _u64, C.c_char_p, _u64, _vp, _vp]),
+    "fhe_encrypt_symmetric_scratch_bytes": (_sz, [_vp, _u64]),
+    "fhe_encrypt_symmetric_batch": (_i, [_vp, _vp, _vp, _u64, C.c_char_p, C.c_char_p, _u64, _vp, _vp, _sz, _vp]),
     "fhe_ctx_modulus_bits": (_u32, [_vp]),
     "fhe_decrypt_scratch_bytes": (_sz, [_vp, _u32, _u64]),
     "fhe_decrypt_batch": (_i, [_vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp, _sz, _vp]),

@@ -165,8 +165,10 @@ def send_jpeg(ctx, encryptor, encoder, rgb, out_path):
     import torch
     h, w, _ = rgb.shape
     chans = [blocks_of(rgb[:, :, c].astype(np.float64), w, h) for c in range(3)]
+    first = _seed_start(encryptor)
     with open(out_path, "wb") as f:
         _encrypt_values(ctx, encryptor, encoder, [v for b in range(len(chans[0])) for c in range(3) for v in chans[c][b]], f)
+    _seed_finish(encryptor, first, out_path)
     return len(chans[0])
 
 
@@ -203,7 +205,8 @@ def rms_error(a, b):
 # ------------------------------------------------------------------------------------------------
 def _encrypt_values(ctx, encryptor, encoder, values, f, chunk=1024):
     """encode + encrypt + write, in stream order.  A keys.DeviceEncryptor (anything with `encrypt_values`) works in device batches
-    (fhe_frac_encode_batch + fhe_encrypt_batch, one download per chunk); a keys.Encryptor one ciphertext at a time."""
+    (fhe_frac_encode_batch + fhe_encrypt_batch, one download per chunk); a keys.Encryptor one ciphertext at a time.  A
+    keys.SymmetricEncryptor (`seeded`) writes records of ONE polynomial, c0; the callers write the seed beside the stream (write_seed)."""
     import torch
     if hasattr(encryptor, "encrypt_values"):
         if (encryptor.int_coeffs, encryptor.frac_coeffs) != (encoder.int_coeffs, encoder.frac_coeffs):
@@ -211,6 +214,8 @@ def _encrypt_values(ctx, encryptor, encoder, values, f, chunk=1024):
         values = [float(v) for v in values]
         for s in range(0, len(values), chunk):
             cts = encryptor.encrypt_values(values[s:s + chunk])
+            if getattr(encryptor, "seeded", False):
+                cts = cts.c0[:, None]                            # [count, 1, k, n]: the existing record format with polys = 1
             torch.cuda.synchronize()
             for ct in cts.cpu().numpy().view(np.uint64):
                 server.write_ciphertext(f, ct)
@@ -221,12 +226,47 @@ def _encrypt_values(ctx, encryptor, encoder, values, f, chunk=1024):
         server.write_ciphertext(f, ct.cpu().numpy().view(np.uint64))
 
 
+# ---- seeded streams (keys.SymmetricEncryptor): records of c0 alone, and 40 bytes beside them -------------------------
+SEED_SUFFIX = ".seed"
+SEED_BYTES = 40
+
+
+def write_seed(path, a_key, first_index):
+    """the sidecar of a seeded stream: the public a_key (32 bytes), then the number of the stream's first ciphertext as a little-endian
+    u64 -- record r expands with index first_index + r (Evaluator.expand_seeded, server_jpeg(seeded="sidecar"))"""
+    a_key = bytes(a_key)
+    if len(a_key) != 32:
+        raise ValueError("a_key has 32 bytes")
+    with open(path, "wb") as f:
+        f.write(a_key + (int(first_index) & ((1 << 64) - 1)).to_bytes(8, "little"))
+
+
+def read_seed(path):
+    """(a_key, first_index) of write_seed; a file of any other length is refused"""
+    with open(path, "rb") as f:
+        raw = f.read(SEED_BYTES + 1)
+    if len(raw) != SEED_BYTES:
+        raise ValueError("%s: a seed file has %d bytes (a_key, first_index)" % (path, SEED_BYTES))
+    return raw[:32], int.from_bytes(raw[32:], "little")
+
+
+def _seed_start(encryptor):
+    return encryptor.next if getattr(encryptor, "seeded", False) else None
+
+
+def _seed_finish(encryptor, first, out_path):
+    if first is not None:
+        write_seed(os.fspath(out_path) + SEED_SUFFIX, encryptor.a_key, first)
+
+
 def send_resize(ctx, encryptor, encoder, rgb, out_path):
     """homo/client_resize.cpp:141-158: every sample of the image encoded and encrypted, "RGBRGB... row by row" (:141),
     the stream server.server_resize reads.  rgb: uint8 [H, W, 3].  Returns (width, height)."""
     h, w, _ = rgb.shape
+    first = _seed_start(encryptor)
     with open(out_path, "wb") as f:
         _encrypt_values(ctx, encryptor, encoder, np.asarray(rgb, dtype=np.uint8).reshape(-1), f)
+    _seed_finish(encryptor, first, out_path)
     return w, h
 
 
@@ -312,11 +352,13 @@ def send_decode(ctx, encryptor, encoder, rgb, out_path):
     h, w, _ = rgb.shape
     flat = np.asarray(rgb, dtype=np.uint8).reshape(-1, 3)
     pairs = []
+    first = _seed_start(encryptor)
     with open(out_path, "wb") as f:
         for ch in range(3):
             runs = run_length_pairs(flat[:, ch])
             pairs.append(len(runs))
             _encrypt_values(ctx, encryptor, encoder, [x for run in runs for x in run], f)
+    _seed_finish(encryptor, first, out_path)
     return w, h, pairs
 
 

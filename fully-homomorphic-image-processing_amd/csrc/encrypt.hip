@@ -186,10 +186,10 @@ template <int L, typename C> struct EncPm {
         for (int r = 0; r < 16; r++) x[0][r] = fold_pm(x[0][r], m);
     }
     static __device__ __forceinline__ u64 mul(u64 x, u64 w, const Mod &m, const Modulus &) { return mulvv_pm(x, w, m); }      // below RQ / 16 q
-    static __device__ __forceinline__ void inv(u64 (&x)[2][16], const RnsBase &b, u32 p, const Mod &m, u64 *lds, int tid) {
-        ntt_inv_regs_pm<L, 2, C::RQ, C::XB, C::LIM, C::RQ>(x, b.itw_pm + (size_t)p * N, m, lds, tid);
+    template <int M> static __device__ __forceinline__ void inv(u64 (&x)[M][16], const RnsBase &b, u32 p, const Mod &m, u64 *lds, int tid) {
+        ntt_inv_regs_pm<L, M, C::RQ, C::XB, C::LIM, C::RQ>(x, b.itw_pm + (size_t)p * N, m, lds, tid);
 #pragma unroll
-        for (int j = 0; j < 2; j++)
+        for (int j = 0; j < M; j++)
 #pragma unroll
             for (int r = 0; r < 16; r++) x[j][r] = canon_rq_pm<C::RQ>(x[j][r], m);
     }
@@ -205,10 +205,10 @@ template <int L> struct EncShoup {
         for (int r = 0; r < 16; r++) x[0][r] = canon_below_64q(x[0][r], m.m.q, m.cs);
     }
     static __device__ __forceinline__ u64 mul(u64 x, u64 w, const Mod &, const Modulus &md) { return mul_barrett(x, w, md); }  // canonical
-    static __device__ __forceinline__ void inv(u64 (&x)[2][16], const RnsBase &b, u32 p, const Mod &m, u64 *lds, int tid) {
-        ntt_inv_regs4m<L, 2, true>(x, b.itw + (size_t)p * N, m.m, lds, tid);      // [0, 4q) in and out
+    template <int M> static __device__ __forceinline__ void inv(u64 (&x)[M][16], const RnsBase &b, u32 p, const Mod &m, u64 *lds, int tid) {
+        ntt_inv_regs4m<L, M, true>(x, b.itw + (size_t)p * N, m.m, lds, tid);      // [0, 4q) in and out
 #pragma unroll
-        for (int j = 0; j < 2; j++)
+        for (int j = 0; j < M; j++)
 #pragma unroll
             for (int r = 0; r < 16; r++) x[j][r] = csub(csub(x[j][r], 2 * m.m.q), m.m.q);
     }
@@ -307,6 +307,171 @@ __global__ __launch_bounds__(NttShape<L>::TP, OCC) void k_enc_fused(ChaChaKey ke
             c1[r * TP] = addmod(y[1][r], nv < 0 ? q - (u64)(-nv) : (u64)nv, q);
         }
         ntt_lds_release();
+    }
+}
+
+// ---- seeded symmetric encryption (include/fhe_hip.h "seeded symmetric encryption") ---------------------------------
+// A fresh symmetric ciphertext is (Delta m' - (a s + e), a) with a uniform: only c0 and the 32-byte key of a's stream travel.
+// a_i[j] = D mod q_i, D = the 128-bit little-endian integer at bytes [16 (i n + j), + 16) of the ChaCha20 stream (a_key, nonce = number
+// of the ciphertext): cipher block B of that stream holds the residues 4 B .. 4 B + 3 of the [k][n] array, so the residues of the first
+// k' primes are the same in every context that shares them.
+__device__ __forceinline__ void seed_block(const ChaChaKey &key, u64 block, u64 nonce, const Modulus &m, u64 (&a)[4]) {
+    u64 r[8];
+    chacha20_block(key, block, nonce, r);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = reduce128(r[2 * i + 1], r[2 * i], m);
+}
+
+// one thread = one cipher block = four consecutive residues of one (ciphertext, prime), two 16-byte stores: a wave writes 2 KiB
+// contiguously (n / 4 is a multiple of 64: one prime per wave).  out: [count][polys][k][n] with a in polynomial polys - 1; with c0
+// ([count][k][n]) given and polys = 2, the same thread copies its four words of c0 into polynomial 0.
+__global__ __launch_bounds__(256) void k_seed_expand(ChaChaKey key, u64 first_index, u64 count, const u64 *__restrict__ c0, u64 *__restrict__ out, u32 polys,
+                                                     const Modulus *__restrict__ mods, u32 k, u32 n) {
+    const u64 row = n / 4, per = (u64)k * row, total = count * per;
+    for (u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (u64)gridDim.x * blockDim.x) {
+        const u64 e = g / per, b = g % per, p = b / row, j = (b % row) * 4;
+        u64 a[4];
+        seed_block(key, b, first_index + e, mods[p], a);
+        ulonglong2 *dst = (ulonglong2 *)(out + ((e * polys + (polys - 1)) * k + p) * n + j);
+        dst[0] = make_ulonglong2(a[0], a[1]);
+        dst[1] = make_ulonglong2(a[2], a[3]);
+        if (c0) {
+            const ulonglong2 *src = (const ulonglong2 *)(c0 + (e * k + p) * n + j);
+            ulonglong2 *d0 = (ulonglong2 *)(out + ((e * polys) * k + p) * n + j);
+            d0[0] = src[0];
+            d0[1] = src[1];
+        }
+    }
+}
+
+// the client's half in ONE launch per batch, on the geometry of k_enc_fused: one workgroup = one encryption, n / 16 threads, sixteen
+// coefficients per thread in the transforms' register mapping.  The noise e (draws n .. 2 n - 1 of the stream (noise_key, index): the e1
+// draw of the public-key sampler, n / 8 cipher blocks) is drawn once and kept as sixteen bytes per thread.  Then per prime: four cipher
+// blocks per thread = sixteen residues of a in natural order, through the transform buffer to the strided mapping, forward transform,
+// times s per slot, inverse transform, c0 = Delta m' - (a s) - e, n residues written.  a itself is never written: the server regenerates it.
+template <int L, typename A, int OCC>
+__global__ __launch_bounds__(NttShape<L>::TP, OCC) void k_enc_sym_fused(ChaChaKey akey, ChaChaKey nkey, u64 first_index, u64 *__restrict__ c0,
+                                                                       const u64 *__restrict__ plain, const u64 *__restrict__ sk_ntt, RnsBase base, EncLift Lf) {
+    __shared__ __align__(16) u64 lds[NttShape<L>::LDS_WORDS];
+    constexpr int N = NttShape<L>::N, TP = NttShape<L>::TP, PER = N / 8;
+    const int tid0 = threadIdx.x;
+    const u64 e = blockIdx.x;
+    const u32 k = base.count;
+#pragma unroll 1
+    for (int j = 0; j < 2; ++j) {
+        const int g = tid0 + j * TP;                              // 2 TP = PER blocks
+        u64 r[8];
+        chacha20_block(nkey, (u64)(PER + g), first_index + e, r);
+        u64 packed = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) packed |= (u64)(unsigned char)draw_noise(r[i]) << (8 * i);
+        lds[g] = packed;
+    }
+    __syncthreads();
+    u32 d1[4];                                                   // byte r: the noise at coefficient r * TP + tid
+    {
+        const signed char *bytes = (const signed char *)lds;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            u32 a = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a |= (u32)(unsigned char)bytes[(4 * w + i) * TP + tid0] << (8 * i);
+            d1[w] = a;
+        }
+    }
+    __syncthreads();                                             // the buffer goes to the residues of a
+#pragma unroll 1
+    for (u32 p = 0; p < k; ++p) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) asm volatile("" : "+v"(d1[w]));      // as in k_enc_fused: unpacked where they are used, not before the loop
+        int tid = tid0;
+        asm volatile("" : "+v"(tid));
+        const typename A::Mod m = A::mod(base, p);
+        const Modulus md = base.mod[p];
+        const u64 q = A::q(m);
+#pragma unroll 1
+        for (int j = 0; j < 4; ++j) {                            // residues 16 tid + 4 j .. + 3 of prime p: block (p N + 16 tid) / 4 + j of the stream
+            u64 a[4];
+            seed_block(akey, (u64)p * (N / 4) + 4 * (u64)tid + j, first_index + e, md, a);
+            ulonglong2 *dst = (ulonglong2 *)(lds + 16 * tid + 4 * j);
+            dst[0] = make_ulonglong2(a[0], a[1]);
+            dst[1] = make_ulonglong2(a[2], a[3]);
+        }
+        __syncthreads();
+        u64 x[1][16];
+#pragma unroll
+        for (int r = 0; r < 16; r++) x[0][r] = lds[r * TP + tid];
+        __syncthreads();                                         // CONTRACT of the transforms: no wave still reads the buffer on entry
+        A::fwd(x, base, p, m, lds, tid);
+        const u64 *s = sk_ntt + (size_t)p * N + tid;
+#pragma unroll
+        for (int r = 0; r < 16; r++) x[0][r] = A::mul(x[0][r], s[r * TP], m, md);
+        A::inv(x, base, p, m, lds, tid);                         // after a forward transform: no barrier needed
+        u64 *o = c0 + (e * k + p) * N + tid;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int nv = enc_byte(d1, r);                      // c0 = Delta m' - a s - e
+            u64 v = negmod(x[0][r], q);
+            if (nv) v = addmod(v, nv < 0 ? (u64)(-nv) : q - (u64)nv, q);
+            if (plain) {
+                const u64 mm = plain[e * N + r * TP + tid];
+                if (mm) {
+                    u64 lift = mul_barrett(Lf.delta[p], mm % q, md);
+                    if (mm >= Lf.threshold) lift = addmod(lift, Lf.increment[p], q);
+                    v = addmod(v, lift, q);
+                }
+            }
+            o[r * TP] = v;
+        }
+        ntt_lds_release();
+    }
+}
+
+// the composition of launches (59 .. 61-bit primes, FHE_SYM_UNFUSED=1): k_seed_expand into scratch, fhe_ntt_forward, k_sym_sk_mul,
+// fhe_ntt_inverse into c0, k_sym_finish -- the same streams, the same exact arithmetic, the same bits
+__global__ __launch_bounds__(256) void k_sym_sk_mul(u64 *__restrict__ a_ntt, const u64 *__restrict__ sk_ntt, const Modulus *__restrict__ mods, u32 k, u32 n,
+                                                    u64 count) {
+    const u64 rows = count * k;
+    for (u64 rp = blockIdx.y; rp < rows; rp += gridDim.y) {
+        const u32 p = (u32)(rp % k);
+        const Modulus m = mods[p];
+        u64 *a = a_ntt + rp * n;
+        const u64 *s = sk_ntt + (u64)p * n;
+        for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) a[i] = mul_barrett(a[i], s[i], m);
+    }
+}
+// one thread = eight consecutive coefficients of encryption e: its noise block, every residue; c0 holds a s on entry
+__global__ __launch_bounds__(256) void k_sym_finish(ChaChaKey nkey, u64 first_index, u64 count, u64 *__restrict__ c0, const u64 *__restrict__ plain,
+                                                    const Modulus *__restrict__ mods, u32 k, u32 n, EncLift L) {
+    const u64 per = n / 8, total = count * per;
+    for (u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (u64)gridDim.x * blockDim.x) {
+        const u64 b = g % per, e = g / per;
+        u64 r[8];
+        chacha20_block(nkey, per + b, first_index + e, r);
+        int v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = draw_noise(r[i]);
+        u64 m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (plain) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) m[i] = plain[e * n + b * 8 + i];
+        }
+        for (u32 p = 0; p < k; ++p) {
+            const Modulus md = mods[p];
+            const u64 q = md.q;
+            u64 *dst = c0 + (e * k + p) * n + b * 8;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                u64 x = negmod(dst[i], q);
+                if (v[i]) x = addmod(x, v[i] < 0 ? (u64)(-v[i]) : q - (u64)v[i], q);
+                if (m[i]) {
+                    u64 lift = mul_barrett(L.delta[p], m[i] % q, md);
+                    if (m[i] >= L.threshold) lift = addmod(lift, L.increment[p], q);
+                    x = addmod(x, lift, q);
+                }
+                dst[i] = x;
+            }
+        }
     }
 }
 
@@ -566,6 +731,95 @@ extern "C" int fhe_encrypt_draws(const fhe_ctx *c, const uint8_t key[32], uint64
     if (!count) return FHE_OK;
     if (c->n % 8) return fail(FHE_ERR_PARAM, "n must be a multiple of 8");
     k_enc_draws<<<blocks_for(count * 3 * (c->n / 8)), 256, 0, (hipStream_t)s>>>(load_key(key), first_index, count, (signed char *)d_draws, c->n);
+    KERNEL_CHECK();
+    return FHE_OK;
+}
+
+// ---- seeded symmetric encryption ----------------------------------------------------------------------------------------------
+namespace {
+// k_seed_expand's grid: enough workgroups to fill the device several times over (the kernel is issue-bound), the rest by the grid-stride loop
+constexpr u64 SEED_MAX_BLOCKS = 8192;
+// what reduce128 and the 16-byte stores need of the context
+int seed_check(const fhe_ctx *c) {
+    if (c->n % 256) return fail(FHE_ERR_PARAM, "n must be a multiple of 256");
+    for (u32 i = 0; i < c->k; ++i)
+        if (!(c->qb.primes[i] >> 32)) return fail(FHE_ERR_PARAM, "modulus %u is below 2^32: the 128-bit reduction of the seeded expansion needs 33 bits", i);
+    return FHE_OK;
+}
+int seed_expand_launch(const fhe_ctx *c, const u64 *c0, u64 count, const uint8_t a_key[32], u64 first_index, u64 *out, u32 polys, hipStream_t st) {
+    const u64 threads = count * c->k * (c->n / 4), b = (threads + 255) / 256;
+    k_seed_expand<<<(unsigned)(b > SEED_MAX_BLOCKS ? SEED_MAX_BLOCKS : b), 256, 0, st>>>(load_key(a_key), first_index, count, c0, out, polys, c->qb.d_mod, c->k, c->n);
+    KERNEL_CHECK();
+    return FHE_OK;
+}
+}  // namespace
+
+extern "C" int fhe_expand_seeded(const fhe_ctx *c, const uint64_t *d_c0, uint64_t count, const uint8_t a_key[32], uint64_t first_index, uint64_t *d_out,
+                                 fhe_stream s) {
+    if (!c || !a_key || (!d_c0 && count) || (!d_out && count)) return fail(FHE_ERR_PARAM, "null argument");
+    if (!count) return FHE_OK;
+    if (int rc = seed_check(c)) return rc;
+    const u64 words = count * c->k * c->n;
+    if (words / c->k / c->n != count || words >> 59) return fail(FHE_ERR_PARAM, "count too large");
+    if (((uintptr_t)d_c0 | (uintptr_t)d_out) & 15) return fail(FHE_ERR_PARAM, "d_c0 and d_out must be 16-byte aligned");
+    if (overlap(d_c0, words, d_out, 2 * words)) return fail(FHE_ERR_PARAM, "d_c0 and d_out overlap");
+    return seed_expand_launch(c, (const u64 *)d_c0, count, a_key, first_index, (u64 *)d_out, 2, (hipStream_t)s);
+}
+
+extern "C" int fhe_seed_expand_a(const fhe_ctx *c, uint64_t count, const uint8_t a_key[32], uint64_t first_index, uint64_t *d_a, fhe_stream s) {
+    if (!c || !a_key || (!d_a && count)) return fail(FHE_ERR_PARAM, "null argument");
+    if (!count) return FHE_OK;
+    if (int rc = seed_check(c)) return rc;
+    const u64 words = count * c->k * c->n;
+    if (words / c->k / c->n != count || words >> 60) return fail(FHE_ERR_PARAM, "count too large");
+    if ((uintptr_t)d_a & 15) return fail(FHE_ERR_PARAM, "d_a must be 16-byte aligned");
+    return seed_expand_launch(c, nullptr, count, a_key, first_index, (u64 *)d_a, 1, (hipStream_t)s);
+}
+
+extern "C" size_t fhe_encrypt_symmetric_scratch_bytes(const fhe_ctx *c, uint64_t count) { return c ? (size_t)count * c->k * c->n * sizeof(u64) : 0; }
+
+extern "C" int fhe_encrypt_symmetric_batch(const fhe_ctx *c, const uint64_t *d_sk_ntt, const uint64_t *d_plain, uint64_t count, const uint8_t a_key[32],
+                                           const uint8_t noise_key[32], uint64_t first_index, uint64_t *d_c0, void *scratch, size_t scratch_bytes, fhe_stream s) {
+    if (!c || !d_sk_ntt || !a_key || !noise_key || (!d_c0 && count)) return fail(FHE_ERR_PARAM, "null argument");
+    if (!count) return FHE_OK;
+    if (!scratch || scratch_bytes < fhe_encrypt_symmetric_scratch_bytes(c, count)) return fail(FHE_ERR_PARAM, "scratch too small: need fhe_encrypt_symmetric_scratch_bytes()");
+    if (first_index + count < first_index) return fail(FHE_ERR_PARAM, "encryption index wraps: an (a_key, index) pair would repeat");
+    if (int rc = seed_check(c)) return rc;
+    if (((uintptr_t)d_c0 | (uintptr_t)scratch) & 15) return fail(FHE_ERR_PARAM, "d_c0 and scratch must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)s;
+    const ChaChaKey nk = load_key(noise_key);
+    EncLift lift;
+    lift.threshold = c->upper_half_threshold;
+    for (u32 i = 0; i < FHE_MAX_K; ++i) { lift.delta[i] = i < c->k ? c->delta_mod[i] : 0; lift.increment[i] = i < c->k ? c->upper_half_increment[i] : 0; }
+    // one launch where k_enc_fused has register transforms for the base (the conditions of fhe_encrypt_batch); FHE_SYM_UNFUSED=1 and 59..61-bit
+    // primes take the composition below -- same bits
+    bool shoup_ok = c->max_prime_bits <= 58;
+    for (u32 i = 0; i < c->k; ++i) shoup_ok = shoup_ok && (c->qb.primes[i] >> 33);
+    if (!c->opt.sym_unfused && count <= 0x7fffffffULL && (shoup_ok || (c->qb.pm_class && !c->opt.ntt_nopm))) {
+        const RnsBase base = c->qb.dev();
+        const ChaChaKey ak = load_key(a_key);
+#define GO_SYM(AA, OCC) DISPATCH_L(c->logn, (k_enc_sym_fused<L, AA<L>, OCC><<<(unsigned)count, NttShape<L>::TP, 0, st>>>(ak, nk, first_index, (u64 *)d_c0, (const u64 *)d_plain, (const u64 *)d_sk_ntt, base, lift)))
+#define GO_SYM2(AA) do { if (c->opt.enc_occ4) { GO_SYM(AA, 4); } else { GO_SYM(AA, 2); } } while (0)
+        if (c->qb.pm_class == 1 && !c->opt.ntt_nopm) { GO_SYM2(EncPmA); }
+        else if (c->qb.pm_class == 2 && !c->opt.ntt_nopm) { GO_SYM2(EncPmB); }
+        else { GO_SYM2(EncShoup); }
+#undef GO_SYM2
+#undef GO_SYM
+        KERNEL_CHECK();
+        return FHE_OK;
+    }
+    u64 *a = (u64 *)scratch;
+    int rc = seed_expand_launch(c, nullptr, count, a_key, first_index, a, 1, st);
+    if (rc) return rc;
+    if ((rc = fhe_ntt_forward(c, (const uint64_t *)a, (uint64_t *)a, count, s))) return rc;
+    {
+        const u64 rows = count * c->k;
+        dim3 grid((c->n + 255) / 256, (unsigned)(rows < 32768 ? rows : 32768));
+        k_sym_sk_mul<<<grid, 256, 0, st>>>(a, (const u64 *)d_sk_ntt, c->qb.d_mod, c->k, c->n, count);
+        KERNEL_CHECK();
+    }
+    if ((rc = fhe_ntt_inverse(c, (const uint64_t *)a, d_c0, count, s))) return rc;
+    k_sym_finish<<<blocks_for(count * (c->n / 8)), 256, 0, st>>>(nk, first_index, count, (u64 *)d_c0, (const u64 *)d_plain, c->qb.d_mod, c->k, c->n, lift);
     KERNEL_CHECK();
     return FHE_OK;
 }

@@ -9,15 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
-struct Modulus {
-    u64 q;      // prime < 2^61
-    u64 mu;     // floor(2^(2b) / q), b = bit length of q  (b <= 61, so mu < 2^62)
-    u32 s1;     // b - 1
-    u32 s2;     // b + 1
-};
+#include "reduce128.h"      // u64, u32, struct Modulus, reduce128 (host and device)
 
 __device__ __forceinline__ u64 csub(u64 x, u64 q) { return x >= q ? x - q : x; }
 __device__ __forceinline__ u64 addmod(u64 a, u64 b, u64 q) { return csub(a + b, q); }

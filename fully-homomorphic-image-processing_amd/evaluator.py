@@ -1037,6 +1037,25 @@ class Evaluator:
         _lib.call("fhe_mod_switch", self.ctx.h, k_out, _ptr(ct), _ptr(out), ct.numel() // (k * n), _stream())
         return out
 
+    def expand_seeded(self, c0, a_key, first_index, out=None):
+        """Seeded fresh ciphertexts to ordinary ones (fhe_expand_seeded): c0 [..., k, n] (what keys.SymmetricEncryptor made,
+        canonical residues) -> [..., 2, k, n] with c0 in polynomial 0 and a = the expansion of (a_key, first_index + i) in polynomial 1, i the
+        flat number of the ciphertext in `c0`.  `out` may not overlap `c0`."""
+        k, n = self.ctx.k, self.ctx.n
+        if not (isinstance(c0, torch.Tensor) and c0.dim() >= 2 and tuple(c0.shape[-2:]) == (k, n) and c0.dtype == torch.int64 and c0.is_contiguous()
+                and c0.device == self.ctx.device):
+            raise ValueError("expand_seeded: `c0` must be a contiguous int64 tensor [..., k, n] = [..., %d, %d] on the context's device, got %r"
+                             % (k, n, tuple(getattr(c0, "shape", ()))))
+        a_key = bytes(a_key)
+        if len(a_key) != 32:
+            raise ValueError("expand_seeded: a_key has 32 bytes")
+        shape = tuple(c0.shape[:-2]) + (2, k, n)
+        if out is not None and (tuple(out.shape) != shape or out.dtype != c0.dtype or not out.is_contiguous() or out.device != c0.device):
+            raise ValueError("expand_seeded: `out` must be a contiguous int64 tensor %r on the input's device, got %r" % (shape, tuple(out.shape)))
+        out = torch.empty(shape, dtype=torch.int64, device=c0.device) if out is None else out
+        _lib.call("fhe_expand_seeded", self.ctx.h, _ptr(c0), c0.numel() // (k * n), a_key, int(first_index) & ((1 << 64) - 1), _ptr(out), _stream())
+        return out
+
     # -- primitives named by the north star ---------------------------------------------------------
     def cubic_coeffs(self, A, B, C, D):
         """a = 3B - A - 3C + D, b = 2A - 5B + 4C - D, c = C - A of Cubic (homo/fhe_resize.h:150-172) in one

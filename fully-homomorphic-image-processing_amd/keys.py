@@ -397,6 +397,83 @@ class DeviceEncryptor:
         return d.cpu().numpy()
 
 
+class SeededCiphertexts:
+    """A batch of fresh symmetric encryptions in their travelling form: `c0` [count, k, n] (device tensor) and the public seed of their
+    second polynomials -- ciphertext i is (c0[i], a) with a = the expansion of (a_key, first_index + i); DESIGN.md 3.18."""
+
+    def __init__(self, c0, a_key, first_index):
+        self.c0, self.a_key, self.first_index = c0, bytes(a_key), int(first_index)
+
+    def __len__(self):
+        return int(self.c0.shape[0])
+
+    def expand(self, evaluator, out=None):
+        """[count, 2, k, n]: the ordinary ciphertexts (Evaluator.expand_seeded)"""
+        return evaluator.expand_seeded(self.c0, self.a_key, self.first_index, out=out)
+
+
+class SymmetricEncryptor:
+    """Fresh encryptions under the SECRET key, at half the bytes (include/fhe_hip.h fhe_encrypt_symmetric_batch) -- what a
+    CLIENT can do: (c0, c1) = (Delta m' - (a s + e), a) with a expanded from the public `a_key` and the number of the ciphertext, so only c0
+    and (a_key, first_index) travel and the server regenerates a (Evaluator.expand_seeded).  e comes from the stream of the secret
+    `noise_key`, which never leaves the client.  Both keys are 32 bytes from the operating system's generator unless given; the index only
+    counts UPWARDS -- an (a_key, index) pair used twice under one secret key reveals the difference of the two plaintexts -- unless the
+    encryptor was made with reproducible=True (tests, seeded benchmark runs; needs both keys), the rule of DeviceEncryptor.
+    `secret_key`: [k, n] coefficient form, as Decryptor takes it; in a level context, sk[:k']."""
+
+    seeded = True
+
+    def __init__(self, ctx, secret_key, a_key=None, noise_key=None, int_coeffs=None, frac_coeffs=None, reproducible=False):
+        self.ctx = ctx
+        _check_key(ctx, secret_key, 1, "SymmetricEncryptor: secret key")
+        self._sk_ntt = _ntt(ctx, secret_key[None].contiguous())[0]
+        if reproducible and (a_key is None or noise_key is None):
+            raise ValueError("reproducible=True needs explicit keys (the OS generator's keys are never reused)")
+        self.reproducible = bool(reproducible)
+        self.a_key = os.urandom(32) if a_key is None else bytes(a_key)
+        self._noise_key = os.urandom(32) if noise_key is None else bytes(noise_key)
+        if len(self.a_key) != 32 or len(self._noise_key) != 32:
+            raise ValueError("a_key and noise_key have 32 bytes each")
+        self.next = 0
+        self.int_coeffs = 100 if int_coeffs is None else int(int_coeffs)
+        self.frac_coeffs = 100 if frac_coeffs is None else int(frac_coeffs)
+        self._scratch = None
+
+    def seek(self, i):
+        if not self.reproducible:
+            raise RuntimeError("seek could repeat an (a_key, index) pair -- the same a under two plaintexts reveals their difference; only an "
+                               "encryptor made with reproducible=True (tests, seeded runs) may position its stream")
+        self.next = int(i)
+
+    def _run(self, plain, count):
+        ctx = self.ctx
+        c0 = torch.empty((count, ctx.k, ctx.n), dtype=torch.int64, device=ctx.device)
+        first = self.next
+        if count:
+            need = int(_lib.load().fhe_encrypt_symmetric_scratch_bytes(ctx.h, count))
+            if self._scratch is None or self._scratch.numel() * 8 < need:
+                self._scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=ctx.device)
+            _lib.call("fhe_encrypt_symmetric_batch", ctx.h, _ptr(self._sk_ntt), _ptr(plain) if plain is not None else None, count, self.a_key, self._noise_key,
+                      first, _ptr(c0), _ptr(self._scratch), self._scratch.numel() * 8, _stream())
+            self.next += count
+        return SeededCiphertexts(c0, self.a_key, first)
+
+    def encrypt_values(self, values):
+        """SeededCiphertexts of Enc(encode(v)) for every v (FractionalEncoder::encode on the device)"""
+        vals = np.ascontiguousarray(values, dtype=np.float64)
+        plain = torch.empty((len(vals), self.ctx.n), dtype=torch.int64, device=self.ctx.device)
+        if len(vals):
+            _lib.call("fhe_frac_encode_batch", self.ctx.h, vals.ctypes.data_as(C.c_void_p), len(vals), self.int_coeffs, self.frac_coeffs, _ptr(plain), _stream())
+        return self._run(plain, len(vals))
+
+    def encrypt_plains(self, plains):
+        """plains: [count, n] device tensor of coefficients below t"""
+        return self._run(plains.contiguous(), int(plains.shape[0]))
+
+    def encrypt_zeros(self, count):
+        return self._run(None, int(count))
+
+
 class Decryptor:
     def __init__(self, ctx, secret_key):
         self.ctx = ctx

@@ -13,6 +13,9 @@
 //   block8x8_scalar, channel_mix transform): groups of 64 ciphertexts packed by block position, planes of a colour conversion; dct8_matrix
 //   seal::hip::PlaneMapPlan,     sparse integer maps across position-packed ciphertexts (fhe_plane_map): packed resize, tile filters
 //   plane_map
+//   seal::hip::SymmetricEncryptor, seeded symmetric encryption (fhe_encrypt_symmetric_batch / fhe_expand_seeded): the client sends c0 and a
+//   encrypt_symmetric,           32-byte seed, half the bytes of a fresh ciphertext; the server regenerates the second polynomial
+//   expand_seeded
 //   seal::hip::level_context,    modulus switching (fhe_mod_switch): a batch goes from the context's k primes to its first k_out, into the
 //   mod_switch                   level context, where it decrypts under the same secret key restricted to those primes
 //   seal::hip::SpecialKeys,      key switching with a special prime (fhe_relinearize_sp_poly / fhe_apply_galois_sp), evaluation side: batches of the
@@ -487,6 +490,74 @@ inline CiphertextBatch plane_map(const PlaneMapPlan &plan, const CiphertextBatch
     detail::check(fhe_plane_map(plan.context().state()->h, plan.handle(), frames.ptr(), out.ptr(), frames.size(), count, nullptr), "plane_map");
     return out;
 }
+
+// ---- seeded symmetric encryption (include/fhe_hip.h: fhe_expand_seeded, fhe_encrypt_symmetric_batch) -------------------------------
+// what keys.SymmetricEncryptor / Evaluator.expand_seeded are to the Python host.  A fresh ciphertext made under the SECRET key is
+// (Delta m' - (a s + e), a) with a expanded from a public 32-byte key and the ciphertext's number: only c0 (a batch of size 1) and the seed travel.
+struct SeededBatch {
+    CiphertextBatch c0;                 // [count][1][k][n]
+    std::array<uint8_t, 32> a_key;      // public: travels with c0
+    uint64_t first_index;               // ciphertext i expands with index first_index + i
+};
+// [count][1][k][n] -> [count][2][k][n]: c0 copied into polynomial 0, a regenerated into polynomial 1; one kernel
+inline CiphertextBatch expand_seeded(const SEALContext &ctx, const CiphertextBatch &c0, const uint8_t a_key[32], uint64_t first_index) {
+    if (!c0.of(ctx) || (c0.count() && c0.size() != 1)) throw std::invalid_argument("expand_seeded: a batch of one-polynomial records of this context is wanted");
+    CiphertextBatch out(ctx, c0.count(), 2);
+    detail::check(fhe_expand_seeded(ctx.state()->h, c0.ptr(), c0.count(), a_key, first_index, out.ptr(), nullptr), "expand_seeded");
+    return out;
+}
+inline CiphertextBatch expand_seeded(const SEALContext &ctx, const SeededBatch &b) { return expand_seeded(ctx, b.c0, b.a_key.data(), b.first_index); }
+
+// The client's encryptor.  Both keys come from the operating system's generator unless passed (tests); noise_key never leaves this object, and the
+// index only counts upwards: an (a_key, index) pair used twice under one secret key reveals the difference of the two plaintexts.
+class SymmetricEncryptor {
+public:
+    SymmetricEncryptor(const SEALContext &ctx, const SecretKey &sk, int int_coeffs = 100, int frac_coeffs = 100, const uint8_t *a_key = nullptr,
+                       const uint8_t *noise_key = nullptr, uint64_t first_index = 0)
+        : ctx_(ctx), ic_(int_coeffs), fc_(frac_coeffs), next_(first_index) {
+        const detail::CtxState &s = *ctx.state();
+        if (sk.buf.words() != s.poly_words()) throw std::invalid_argument("secret key does not match the context");
+        sk_ntt_.resize(s.poly_words());
+        detail::check(fhe_ntt_forward(s.h, sk.buf.ptr(), sk_ntt_.ptr(), 1, nullptr), "ntt");
+        if (a_key) std::memcpy(a_key_.data(), a_key, 32);
+        else a_key_ = detail::Sampler::fresh_key();
+        if (noise_key) std::memcpy(noise_key_.data(), noise_key, 32);
+        else noise_key_ = detail::Sampler::fresh_key();
+    }
+    SeededBatch encrypt_values(const std::vector<double> &values) {
+        const detail::CtxState &s = *ctx_.state();
+        detail::DevBuf plain(values.size() * s.n);
+        if (!values.empty()) detail::check(fhe_frac_encode_batch(s.h, values.data(), values.size(), ic_, fc_, plain.ptr(), nullptr), "frac_encode_batch");
+        return run(values.empty() ? nullptr : plain.ptr(), values.size());
+    }
+    SeededBatch encrypt_zeros(size_t count) { return run(nullptr, count); }
+    const std::array<uint8_t, 32> &a_key() const { return a_key_; }
+    uint64_t next_index() const { return next_; }
+private:
+    SeededBatch run(const uint64_t *plain, size_t count) {
+        const detail::CtxState &s = *ctx_.state();
+        SeededBatch out;
+        out.c0.shape(ctx_, count, 1);
+        out.a_key = a_key_;
+        std::lock_guard<std::mutex> lk(mu_);                                 // the stream index and the scratch buffer are per object
+        out.first_index = next_;
+        if (!count) return out;
+        if (next_ + count < next_) throw std::runtime_error("SymmetricEncryptor: the encryption index would wrap");
+        const size_t need = (fhe_encrypt_symmetric_scratch_bytes(s.h, count) + 7) / 8;
+        if (scratch_.words() < need) scratch_.resize(need);
+        detail::check(fhe_encrypt_symmetric_batch(s.h, sk_ntt_.ptr(), plain, count, a_key_.data(), noise_key_.data(), next_, out.c0.ptr(), scratch_.ptr(),
+                                                  scratch_.words() * 8, nullptr), "encrypt_symmetric_batch");
+        next_ += count;
+        return out;
+    }
+    SEALContext ctx_;
+    detail::DevBuf sk_ntt_, scratch_;
+    std::array<uint8_t, 32> a_key_, noise_key_;
+    int ic_, fc_;
+    uint64_t next_;
+    std::mutex mu_;
+};
+inline SeededBatch encrypt_symmetric(SymmetricEncryptor &enc, const std::vector<double> &values) { return enc.encrypt_values(values); }
 
 // ---- modulus switching (include/fhe_hip.h: fhe_mod_switch) ---------------------------------------------------------------------------
 // what SEALContext.level / Evaluator.mod_switch are to the Python host.  The level context is a context of its own; keep it as long as its

@@ -227,7 +227,8 @@ def _stop_pipeline(reader_thread, writer_thread, free_in, to_write):
     torch.cuda.synchronize()
 
 
-def server_jpeg(ctx, in_path, out_path, n_blocks, wave_blocks=8, quant=None, do_dct=True, io_threads=8, slots=3, stats=None, validate=True, out_primes=None):
+def server_jpeg(ctx, in_path, out_path, n_blocks, wave_blocks=8, quant=None, do_dct=True, io_threads=8, slots=3, stats=None, validate=True, out_primes=None,
+                seeded=None):
     """Process `n_blocks` colour blocks.  in_path / out_path: file names, or StreamFile objects a long-lived server keeps
     open (their mappings, and the page-table entries behind them, are then reused from call to call).  Input order per block: 64 R, 64 G, 64 B ciphertexts
     (homo/server_jpeg.cpp:115-124).  Output order per block: 64 Y, 64 Cb, 64 Cr
@@ -247,7 +248,10 @@ def server_jpeg(ctx, in_path, out_path, n_blocks, wave_blocks=8, quant=None, do_
     validate: every uploaded wave is checked for residues that are not below their modulus (fhe_count_unreduced; ValueError at
     the end of the job -- what Ciphertext::load rejects per ciphertext, homo/server_jpeg.cpp:117-123).
     out_primes: None, or the number of primes the output records keep (1 .. k - 1): every output wave is mod-switched on the device before
-    its download, the records carry k = out_primes and belong to ctx.level(out_primes) -- the client decrypts there with sk[:out_primes]."""
+    its download, the records carry k = out_primes and belong to ctx.level(out_primes) -- the client decrypts there with sk[:out_primes].
+    seeded: None, "sidecar" or (a_key, first_index): the input holds seeded fresh ciphertexts (client.send_jpeg with a keys.SymmetricEncryptor:
+    records of ONE polynomial, c0; "sidecar" reads the pair from in_path + ".seed").  Half the bytes travel file -> pinned -> HBM; record r is
+    expanded on the device with index first_index + r (Evaluator.expand_seeded) before the wave's compute.  stats["bytes_in"] is the halved figure."""
     ev = Evaluator(ctx)
     plan = DctPlan(ctx, quant) if do_dct else None
 
@@ -256,17 +260,17 @@ def server_jpeg(ctx, in_path, out_path, n_blocks, wave_blocks=8, quant=None, do_
         if do_dct:
             ev.dct8x8_quant(plan, din.view(nb * 3, 64, 2, ctx.k, ctx.n), out=dout.view(nb * 3, 64, 2, ctx.k, ctx.n))
 
-    return _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, do_dct, io_threads, slots, stats, validate, out_primes)
+    return _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, do_dct, io_threads, slots, stats, validate, out_primes, seeded)
 
 
 def server_jpeg_decompress(ctx, in_path, out_path, n_blocks, quant=None, to_rgb=True, wave_blocks=8, io_threads=8, slots=3, stats=None, validate=True,
-                           out_primes=None):
+                           out_primes=None, seeded=None):
     """The way back: reads what server_jpeg writes (per block 64 Y, 64 Cb, 64 Cr ciphertexts of quantised DCT coefficients) and
     writes what server_jpeg reads (per block 64 R, 64 G, 64 B).  Per wave: fhe_idct8x8_dequant over the 3 * wave channel-blocks
     (dequantisation by `quant`, None: skipped -- pass the table server_jpeg quantised with), then, with to_rgb, fhe_ycc_to_rgb_blocks in
     place on the stream layout.  Same five-stage pipeline, arguments and residue validation as server_jpeg.  Returns blocks processed.
     A server_jpeg + server_jpeg_decompress round trip decrypts to the pixels only with a plain modulus t >= 2^26 (include/fhe_hip.h).
-    out_primes: as server_jpeg's."""
+    out_primes, seeded: as server_jpeg's."""
     ev = Evaluator(ctx)
     plan = IdctPlan(ctx, quant)
 
@@ -275,31 +279,56 @@ def server_jpeg_decompress(ctx, in_path, out_path, n_blocks, quant=None, to_rgb=
         if to_rgb:
             ev.ycc_to_rgb_blocks(dout)                           # in place: R, G, B in the stream's block layout
 
-    return _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, True, io_threads, slots, stats, validate, out_primes)
+    return _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, True, io_threads, slots, stats, validate, out_primes, seeded)
 
 
-def _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, separate_out, io_threads, slots, stats, validate, out_primes=None):
+def _seed_of(seeded, in_path):
+    """seeded=None | "sidecar" | (a_key, first_index) -> None or (a_key, first_index)"""
+    if seeded is None:
+        return None
+    if isinstance(seeded, str):
+        if seeded != "sidecar":
+            raise ValueError("seeded: None, \"sidecar\" or (a_key, first_index), got %r" % (seeded,))
+        if isinstance(in_path, StreamFile):
+            raise ValueError("seeded=\"sidecar\" needs the input stream's file name; pass (a_key, first_index) with a StreamFile")
+        from .client import SEED_SUFFIX, read_seed
+        return read_seed(os.fspath(in_path) + SEED_SUFFIX)
+    a_key, first_index = seeded
+    a_key = bytes(a_key)
+    if len(a_key) != 32:
+        raise ValueError("seeded: a_key has 32 bytes")
+    return a_key, int(first_index)
+
+
+def _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, separate_out, io_threads, slots, stats, validate, out_primes=None, seeded=None):
     """server_jpeg's pipeline over records of 192 ciphertexts per block; compute(din, dout, nb) runs on the main stream for one wave
     (din is dout unless separate_out).  out_primes: the wave's result is mod-switched into a buffer of the level context's shape, which is
-    what the download, the output staging buffers and the writer see."""
+    what the download, the output staging buffers and the writer see.  seeded: the input records hold c0 alone; the staging buffers, the
+    upload and its device buffer have half the size, and the wave is expanded into din on the main stream before `compute` (the residue
+    check reads the half-size buffer: the regenerated polynomial is canonical by construction)."""
     import queue
     import threading
     import time
     residues = _ResidueCheck(ctx, validate)
+    seed = _seed_of(seeded, in_path)
+    in_polys = 1 if seed else 2
     wave_blocks = max(1, min(wave_blocks, n_blocks))
     slots = max(2, slots)
     shape = (wave_blocks, 3, 64, 2, ctx.k, ctx.n)            # wave: block, channel, pixel, poly, prime, coeff
-    hin = [_pinned(("in", i), shape) for i in range(slots)]
+    hshape = (wave_blocks, 3, 64, in_polys, ctx.k, ctx.n)    # what travels: both polynomials, or c0 alone
+    hin = [_pinned(("in", i), hshape) for i in range(slots)]
     octx, out_primes = _out_level(ctx, out_primes)
     oshape = (wave_blocks, 3, 64, 2, octx.k, octx.n)
     hout = [_pinned(("out", i), oshape) for i in range(slots)]
     din = [torch.empty(shape, dtype=torch.int64, device=ctx.device) for _ in range(2)]
+    dup = [torch.empty(hshape, dtype=torch.int64, device=ctx.device) for _ in range(2)] if seed else din      # where the upload lands
+    expander = Evaluator(ctx) if seed else None
     dout = [torch.empty(shape, dtype=torch.int64, device=ctx.device) for _ in range(2)] if separate_out else din
     dlow = [torch.empty(oshape, dtype=torch.int64, device=ctx.device) for _ in range(2)] if out_primes else dout      # what leaves for the host
     switcher = Evaluator(ctx) if out_primes else None
     main = torch.cuda.current_stream()
     h2d, d2h = _copy_streams()
-    rec = RECORD_HEADER + 2 * ctx.k * ctx.n * 8
+    rec = RECORD_HEADER + in_polys * ctx.k * ctx.n * 8
     rec_out = RECORD_HEADER + 2 * octx.k * octx.n * 8
     if (in_path.size if isinstance(in_path, StreamFile) else os.path.getsize(in_path)) < n_blocks * 192 * rec:
         raise EOFError("ciphertext stream ended")
@@ -327,7 +356,7 @@ def _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, separa
                 if copied is not None:
                     copied.synchronize()                        # the previous wave in this slot has left for the device
                 t_io = time.perf_counter()
-                fin.transfer(s * 192, (e - s) * 192, 2, ctx, hin[slot], io_threads)
+                fin.transfer(s * 192, (e - s) * 192, in_polys, ctx, hin[slot], io_threads)
                 io_seconds["read"] += time.perf_counter() - t_io
                 if trace is not None:
                     trace.append(("read", wi, t_io - t0, time.perf_counter() - t0))
@@ -374,7 +403,7 @@ def _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, separa
                 for evt in (computed[d], drained[d]):           # the device buffer is free again
                     if evt is not None:
                         h2d.wait_event(evt)
-                din[d][:nb].copy_(hin[slot][:nb], non_blocking=True)
+                dup[d][:nb].copy_(hin[slot][:nb], non_blocking=True)
                 copied = torch.cuda.Event()
                 copied.record(h2d)
             free_in.put((slot, copied))
@@ -389,7 +418,9 @@ def _block_stream(ctx, in_path, out_path, n_blocks, wave_blocks, compute, separa
             if stats is not None:
                 t_start.append(torch.cuda.Event(enable_timing=True))
                 t_start[-1].record(main)
-            residues.add(din[d][:nb])
+            residues.add(dup[d][:nb])
+            if seed:                                             # record r of the stream is ciphertext first_index + r of the seed
+                expander.expand_seeded(dup[d][:nb].view(nb * 192, ctx.k, ctx.n), seed[0], seed[1] + s * 192, out=din[d][:nb].view(nb * 192, 2, ctx.k, ctx.n))
             compute(din[d][:nb], dout[d][:nb], nb)
             if out_primes:
                 switcher.mod_switch(dout[d][:nb], out_primes, out=dlow[d][:nb])

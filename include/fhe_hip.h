@@ -809,6 +809,32 @@ int fhe_encrypt_batch(const fhe_ctx *ctx, const uint64_t *d_pk_ntt, const uint64
 int fhe_encrypt_draws(const fhe_ctx *ctx, const uint8_t key[32], uint64_t first_index, uint64_t count, int8_t *d_draws,
                       fhe_stream stream);
 
+/* ---- seeded symmetric encryption: fresh ciphertexts at half the bytes -------------------------------------------------
+ * The client holds the secret key, so it can encrypt as (c0, c1) = (Delta m' - (a s + e), a) with a UNIFORM a expanded from a public
+ * 32-byte a_key: only c0 and the key travel, the server regenerates a.  New entry points only (csrc/encrypt.hip).
+ *   a:  ciphertext number e = first_index + i (wrapping modulo 2^64) is the ChaCha20 nonce under a_key (the cipher of fhe_encrypt_batch).
+ *       For prime i and coefficient j, D = the 128-bit little-endian integer at bytes [16 (i n + j), 16 (i n + j) + 16) of that stream and
+ *       a_i[j] = D mod q_i (bias below q_i / 2^128; no rejection, so the stream position never depends on the data).  Coefficient form.
+ *       The residues of the first k' primes do not depend on k: the expansion in a level context is a prefix of the parent's.
+ *   e:  the e1 draw of the sampler above under the SECRET noise_key: draws n .. 2 n - 1 of the stream (noise_key, nonce = e).
+ *   c0 = Delta m' - (a s + e) with the lift of fhe_add_plain, so the phase c0 + c1 s is Delta m' - e in every residue.
+ * An (a_key, index) pair must never be used twice under one secret key: two ciphertexts with the same a reveal the difference of their
+ * plaintexts.  a_key is public and travels with the stream; noise_key never leaves the client.
+ * Primes below 2^32 are refused (the 128-bit reduction needs 33 bits); the device pointers are 16-byte aligned.  Null pointers and a short
+ * scratch are refused with the outputs untouched; count == 0 is a no-op.  Both work in a level context with sk[:k']. */
+/* d_c0: [count][k][n] canonical residues; d_out: [count][2][k][n] (c0 copied into polynomial 0, a into polynomial 1); the ranges must not overlap */
+int fhe_expand_seeded(const fhe_ctx *ctx, const uint64_t *d_c0, uint64_t count, const uint8_t a_key[32],
+                      uint64_t first_index, uint64_t *d_out, fhe_stream stream);
+/* c1 alone: d_a [count][k][n] (tests, and hosts that keep c0 elsewhere) */
+int fhe_seed_expand_a(const fhe_ctx *ctx, uint64_t count, const uint8_t a_key[32], uint64_t first_index,
+                      uint64_t *d_a, fhe_stream stream);
+size_t fhe_encrypt_symmetric_scratch_bytes(const fhe_ctx *ctx, uint64_t count);
+/* d_sk_ntt: [k][n] NTT form (what fhe_decrypt_batch takes); d_plain: [count][n] below t, or NULL for zero; d_c0: [count][k][n].
+ * Refuses a batch whose index would wrap.  FHE_SYM_UNFUSED=1 (read at fhe_ctx_create) runs the composition of launches everywhere. */
+int fhe_encrypt_symmetric_batch(const fhe_ctx *ctx, const uint64_t *d_sk_ntt, const uint64_t *d_plain, uint64_t count,
+                                const uint8_t a_key[32], const uint8_t noise_key[32], uint64_t first_index,
+                                uint64_t *d_c0, void *scratch, size_t scratch_bytes, fhe_stream stream);
+
 /* ---- decryption in batches (the clients' half: homo/client_jpeg.cpp:266-280, homo/client_resize.cpp:190-210) -----------------------
  * seal::Decryptor::decrypt of `count` ciphertexts of `size` polynomials: phase = sum_j c_j s^j (Horner per NTT slot), then
  * m = floor((t x + floor(q/2)) / q) mod t EXACTLY for x = the CRT value of the phase -- formed per coefficient from the residues with
